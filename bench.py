@@ -21,11 +21,15 @@ tmpc_comm_* C ABI (trajoptmpcreference_amd/dist.py; no PyTorch) broadcasts the
 initial states from rank 0, times the region with a barrier and the max over
 ranks, and gathers every problem's exit code / iteration count to rank 0.
 
-Checks carried in the line (rank 0): the CPU leg (oracle NumPy restatement,
-`cpu_baseline`) solves the first S problems of the same workload and
-`parity` compares them with the GPU's exit codes, SQP iteration counts and
-per-QP PCG iteration counts; `kkt_residual` is SURVEY §8d's residual against
-the reference's own first QP.
+A plain run sets up, warms up, times the --steps steps and prints the line;
+--dump-outputs DIR also writes what the last timed step computed.  Everything
+else is behind --full.  Checks carried in the --full line (rank 0): the CPU
+leg (oracle NumPy restatement, `cpu_baseline`) solves the first S problems of
+the same workload and `parity` compares them with the GPU's exit codes, SQP
+iteration counts and per-QP PCG iteration counts; `kkt_residual` is SURVEY
+§8d's residual against the reference's own first QP.  --full also adds the
+stream's check against the lock-step solve, the lock-step and PCIe-inclusive
+rates and the other BASELINE configurations' lines.
 """
 import argparse
 import json
@@ -45,6 +49,7 @@ FP32_PEAK_TFLOPS = 157.3    # MI355X fp32 vector peak (non-packed FMA)
 LDS_PEAK_GBS = 256 * 2.4 * 256   # 256 B/clk/CU (ds_read_b64/b128) x 2.4 GHz x 256 CUs
 MALL_MEASURED_GBS = 8600.0  # Infinity-Cache-resident row gathers, chip-wide (MI355X_MICROARCH.md, Indexed rows)
 CUS = 256
+DUMP_LIMIT_BYTES = 64 * 10 ** 6   # --dump-outputs: all files together stay under this
 
 
 # Soft box-constraint presets (TrajoptConstraint.set_*_limits; |u| <= 0.5 and |q| <= 1.0 are
@@ -66,6 +71,15 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else the benchmark measures or checks: the "
+                         "stream's check against the lock-step solve and the lock-step rate, the PCIe-inclusive rate, "
+                         "the CPU baseline and parity sample, the KKT residual, and the other BASELINE "
+                         "configurations' lines.  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (rank 0's problems) to DIR/<name>.npy, float64, "
+                         f"at most {DUMP_LIMIT_BYTES // 10 ** 6} MB in all (a fixed seeded sample of the problems "
+                         "when they are more)")
     ap.add_argument("--batch", type=int, default=4096, help="problems per GPU")
     ap.add_argument("--N", type=int, default=64)
     ap.add_argument("--links", type=int, default=6)
@@ -815,6 +829,49 @@ def stream_check(ctx, a, d, sbuf, copies, ex_b, it_b, xb):
                         "its input; final x of the first and last copies bitwise"}
 
 
+def timed_outputs(ctx, a, d, sbuf, steps, stream, mpc, trajectories=True):
+    """What the last timed step left on the device, as a caller of the timed path receives it (this rank's B
+    problems): the stream's output rows of its last B problems -- x, u and status (exit code, iterations,
+    exit_soft, outer_iter) --, or the lock-step solve's x and u in place, with the MPC loop's executed states /
+    controls and per-step exit codes / iterations.  Read before anything else touches the buffers.
+    trajectories = False: the integer arrays only."""
+    n, N, B = a.links, a.N, a.batch
+    out = {}
+    if trajectories:
+        x, u = np.empty((B, 2 * n, N)), np.empty((B, n, N - 1))
+        ctx.d2h(x, sbuf["x"] if stream else d["x"], offset=(steps - 1) * x.nbytes if stream else 0)
+        ctx.d2h(u, sbuf["u"] if stream else d["u"], offset=(steps - 1) * u.nbytes if stream else 0)
+        out.update(x=x, u=u)
+    if stream:
+        st = np.empty((B, 4), dtype=np.int32)
+        ctx.d2h(st, sbuf["st"], offset=(steps - 1) * st.nbytes)
+        out["status"] = st
+    if mpc:
+        K1 = a.mpc_steps
+        out.update(exit_codes=np.empty((B, K1), dtype=np.int32), iters=np.empty((B, K1), dtype=np.int32))
+        if trajectories:
+            out.update(x_exec=np.empty((B, 2 * n, K1 + 1)), u_exec=np.empty((B, n, K1)))
+        for k, p in (("x_exec", "xe"), ("u_exec", "ue"), ("exit_codes", "codes"), ("iters", "iters")):
+            if k in out:
+                ctx.d2h(out[k], mpc[p])
+    return out
+
+
+def write_outputs(path, outs):
+    """--dump-outputs: every array [B][...] of `outs` as path/<name>.npy in float64.  Past DUMP_LIMIT_BYTES in
+    all, the same seeded sample of the B problems (problems.npy: their indices) is written of every array."""
+    os.makedirs(path, exist_ok=True)
+    B = next(iter(outs.values())).shape[0]
+    per_problem = 8 * sum(v[0].size for v in outs.values()) + 8
+    keep = (DUMP_LIMIT_BYTES - 256 * (len(outs) + 1)) // per_problem   # less the .npy headers
+    idx = np.arange(B)
+    if keep < B:
+        idx = np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+        np.save(os.path.join(path, "problems.npy"), idx.astype(np.float64))
+    for k, v in outs.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v[idx], dtype=np.float64))
+
+
 STREAM_BASIS = ("continuous batching (tmpc_sqp_solve_stream_device / tmpc_ilqr_solve_stream_device): the timed "
                 "region solves steps x B problems (problem p starts from resident input p mod B) through B resident "
                 "slots; a slot whose problem exits takes the next pending one in the same batch iteration, so the "
@@ -825,10 +882,14 @@ STREAM_BASIS = ("continuous batching (tmpc_sqp_solve_stream_device / tmpc_ilqr_s
                 "time (D2D restore + solve to every problem's exit), the round-5 definition")
 
 
-def run_line(ctx, comm, rank, world, a, steps, warmup, stream, lockstep_steps, substreams=1):
+def run_line(ctx, comm, rank, world, a, steps, warmup, stream, lockstep_steps, substreams=1, full=True, dump=None):
     """Measure workload `a` (B = a.batch problems per rank): the line's value (solves/s over all ranks), its
-    kernel table and work counters, the stream's check against the lock-step solve, and the lock-step rate.
-    Returns (line dict, device inputs, host u0, the lock-step batch's status / x)."""
+    kernel table and work counters and, when `full`, the stream's check against the lock-step solve and the
+    lock-step rate.  Not `full`: nothing runs after the timed steps that they have not already computed -- the
+    gathered exit codes / iteration counts are the last timed step's own (a lock-step SQP / iLQR batch solve
+    returns them to the host only on request, so there the one solve that asks follows the timed steps).
+    dump: the directory rank 0 writes the last timed step's outputs to (write_outputs).
+    Returns (line dict, device inputs, host u0, work counters, kernel table, k_hard_pcg's counted bytes)."""
     setup_workload(ctx, a)
     d, u0 = workload_inputs(ctx, comm, rank, a)
     B, N = a.batch, a.N
@@ -848,14 +909,27 @@ def run_line(ctx, comm, rank, world, a, steps, warmup, stream, lockstep_steps, s
             "mode": "stream" if stream else ("lockstep MPC loop" if mpc else "lockstep")}
     if stream:
         line["substreams"] = substreams
-    # the lock-step batch solve of the same inputs: status for the gather and the stream check
-    ex_b, it_b = batch_solve(ctx, a, d, want_status=True, mpc=mpc)
+    outs = None
+    if dump or (not full and (stream or mpc)):
+        outs = timed_outputs(ctx, a, d, sbuf, steps, stream, mpc, trajectories=bool(dump))
+    if full or not (stream or mpc):
+        # the lock-step batch solve of the same inputs: status for the gather and the stream check
+        ex_b, it_b = batch_solve(ctx, a, d, want_status=True, mpc=mpc)
+    elif stream:
+        ex_b, it_b = outs["status"][:, 0].copy(), outs["status"][:, 1].copy()
+    else:
+        ex_b, it_b = outs["exit_codes"].reshape(-1), outs["iters"].reshape(-1)
+    if dump and rank == 0:
+        if not (stream or mpc):
+            outs.update(exit_code=ex_b, iterations=it_b)
+        write_outputs(dump, outs)
     if stream:
-        xb = np.empty((B, 2 * a.links, N))
-        ctx.d2h(xb, d["x"])
-        line["stream_check"] = stream_check(ctx, a, d, sbuf, steps, ex_b, it_b, xb)   # the timed stream's rows
+        if full:
+            xb = np.empty((B, 2 * a.links, N))
+            ctx.d2h(xb, d["x"])
+            line["stream_check"] = stream_check(ctx, a, d, sbuf, steps, ex_b, it_b, xb)   # the timed stream's rows
         free_stream_buffers(ctx, sbuf)
-        if lockstep_steps > 0:
+        if full and lockstep_steps > 0:
             el, _, _, _ = measure(ctx, comm, a, d, lockstep_steps, 1, False)
             line["lockstep"] = {"value": B * lockstep_steps * world / el, "ms_per_step": 1000.0 * el / lockstep_steps,
                                 "steps": lockstep_steps}
@@ -963,17 +1037,18 @@ def main():
     comm = standin.make_comm(ctx, rank, world, cfg) if standin else dist.make_comm(ctx, rank, world, cfg)
     stream = not a.lockstep and a.mpc_steps == 0
     line, d, u0, counters, kernels, hard_bytes = run_line(ctx, comm, rank, world, a, a.steps, a.warmup, stream,
-                                                          a.lockstep_steps if stream else 0, a.substreams)
+                                                          a.lockstep_steps if stream else 0, a.substreams,
+                                                          full=a.full, dump=a.dump_outputs)
     headline = is_headline(a)
     # ---- PCIe-inclusive rate: the same steps x B problems with host inputs and outputs (H2D of x0 / u0, the
     # stream, D2H of every problem's x, u and status) -- BASELINE.md section 3's wall-time definition
     pcie = None
-    if headline:
+    if headline and a.full:
         xh = x0_host(ctx, d["x0"], B, nx, N)
         pcie = pcie_inclusive(ctx, a, xh, u0, stream)
     comm.barrier()
     extra = {}
-    if headline and not a.no_secondary:
+    if headline and a.full and not a.no_secondary:
         extra = run_config_lines(ctx, comm, rank, world, a)
     if rank != 0:
         comm.close()
@@ -990,10 +1065,10 @@ def main():
     if standin:
         out["standin"] = os.environ.get("TMPC_BENCH_STANDIN")   # a test stand-in context, not libtmpc
     out["roofline"] = line_roofline(a, N, nx, nu, kernels, counters, hard_bytes)
-    if headline:
+    if headline and a.full:
         out["value_pcie_inclusive"] = pcie["value"] if pcie else None
     cpu, par = None, None
-    if headline and not a.no_cpu_baseline and world == 1:
+    if headline and a.full and not a.no_cpu_baseline and world == 1:
         share, total, basis = host_cores()
         procs = a.cpu_procs if a.cpu_procs > 0 else share
         sample = min(B, a.cpu_sample if a.cpu_sample > 0 else 40 * procs)
@@ -1006,7 +1081,7 @@ def main():
         gr = ctx.sqp_solve_batch(x0_host(ctx, d["x0"], B, nx, N)[:sample], u0[:sample], N, dt, a.method)
         par = parity_check(gr, res)
     out["cpu_baseline"] = cpu
-    if headline:
+    if headline and a.full:
         out["parity"] = par
         out["kkt_residual"] = kkt_residual_check(ctx, n)
         out["pcie_inclusive"] = pcie

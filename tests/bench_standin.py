@@ -15,7 +15,8 @@ class Context:
     options = b"bench-standin"
 
     def __init__(self, device=0):
-        if os.environ.get("TMPC_STANDIN_FAIL_RANK") == os.environ.get("RANK"):
+        fail = os.environ.get("TMPC_STANDIN_FAIL_RANK")
+        if fail is not None and fail == os.environ.get("RANK"):
             raise RuntimeError(f"stand-in: rank {os.environ.get('RANK')} fails on purpose")
         self.device = device
         self.mem, self.next = {}, 1

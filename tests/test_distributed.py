@@ -252,6 +252,61 @@ def test_bench_launches_its_own_ranks():
     assert line["iters_mean"] == float(np.mean(iters)) and line["iters_max"] == max(iters)
 
 
+def test_bench_plain_run_dumps_its_last_timed_step_and_full_adds_the_checks(tmp_path):
+    """A plain run times --steps steps and reports nothing that needs a run of its own; --dump-outputs writes
+    the last timed step's x, u and status (float64), equal to the oracle's solves of the same workload and
+    identical from run to run; --full adds the stream check and the lock-step rate to the same line."""
+    from oracle import rbd
+    from oracle import sqp as osqp
+    from trajoptmpcreference_amd.urdf import parse_urdf, planar_arm_urdf
+    B, n, N = 2, 2, 8
+    args = ["--gpus", "1", "--batch", str(B), "--links", str(n), "--N", str(N), "--steps", "2", "--warmup", "1"]
+    rc, plain, err = _run_bench(args + ["--dump-outputs", str(tmp_path / "plain")])
+    assert rc == 0, err[-3000:]
+    assert plain["steps"] == 2 and plain["warmup"] == 1 and plain["ms_per_step"] > 0
+    assert abs(plain["value"] - B * 1000.0 / plain["ms_per_step"]) <= 1e-9 * plain["value"]
+    assert plain["unit"] == "solves/s" and plain["higher_is_better"] is True and plain["dtype"] == "f64"
+    assert plain["problems_gathered"] == B
+    for k in ("stream_check", "lockstep", "parity", "kkt_residual", "pcie_inclusive", "secondary", "config2"):
+        assert k not in plain, k
+    rc, full, err = _run_bench(args + ["--full", "--dump-outputs", str(tmp_path / "full")])
+    assert rc == 0, err[-3000:]
+    assert full["stream_check"]["status_mismatches"] == 0 and full["stream_check"]["x_mismatches"] == 0
+    assert full["lockstep"]["steps"] == 2 and full["exit_codes"] == plain["exit_codes"]
+    m = parse_urdf(planar_arm_urdf(n))
+    cost = osqp.QuadCost(np.eye(2 * n), 100 * np.eye(2 * n), 0.1 * np.eye(n), np.zeros(2 * n))
+    got = {k: np.load(tmp_path / "plain" / (k + ".npy")) for k in ("x", "u", "status")}
+    assert sorted(p.name for p in (tmp_path / "plain").iterdir()) == ["status.npy", "u.npy", "x.npy"]
+    for k, v in got.items():
+        assert v.dtype == np.float64 and v.shape[0] == B
+        assert np.array_equal(v, np.load(tmp_path / "full" / (k + ".npy"))), k
+    for i, q in enumerate(bench.initial_states(n, B, 0)):
+        x = np.zeros((2 * n, N))
+        x[:n, 0] = q
+        for k in range(N - 1):
+            x[:, k + 1] = rbd.euler(m, x[:, k][None], np.zeros((1, n)), 0.1)[0]
+        r = osqp.sqp(m, cost, x, np.zeros((n, N - 1)), N, 0.1, "PCG-SS")
+        assert np.array_equal(got["x"][i], r["x"]) and np.array_equal(got["u"][i], r["u"])
+        assert list(got["status"][i, :2]) == [r["exit_sqp"], r["sqp_iter"]]
+
+
+def test_bench_dump_outputs_samples_the_problems_past_its_size_limit(tmp_path, monkeypatch):
+    """Past the size limit every array is written for the same seeded sample of the problems, whose indices
+    are written beside them; the files together stay under the limit."""
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    B = 64
+    outs = {"x": np.arange(B * 12.0).reshape(B, 4, 3), "status": np.arange(B * 4, dtype=np.int32).reshape(B, 4)}
+    bench.write_outputs(str(tmp_path / "a"), outs)
+    bench.write_outputs(str(tmp_path / "b"), outs)
+    idx = np.load(tmp_path / "a" / "problems.npy").astype(int)
+    assert 0 < idx.size < B and np.all(np.diff(idx) > 0)
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 4096
+    for k, v in outs.items():
+        got = np.load(tmp_path / "a" / (k + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, v[idx])
+        assert np.array_equal(got, np.load(tmp_path / "b" / (k + ".npy")))
+
+
 def test_bench_fails_when_a_rank_fails():
     rc, line, err = _run_bench(["--gpus", "2", "--batch", "2", "--links", "2", "--N", "8", "--steps", "1",
                                 "--warmup", "0"], extra_env={"TMPC_STANDIN_FAIL_RANK": "1"}, timeout=200)
