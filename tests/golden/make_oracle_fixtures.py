@@ -146,7 +146,7 @@ def job_mpc128sqp(seed):
     return dict(seed=seed, exit_codes=o["exit_codes"], iters=o["iters"], x_exec=o["x_exec"], u_exec=o["u_exec"])
 
 
-# SQP past the fused QP's 1536 Schur rows (the banded path, csrc/tmpc_api.cpp qp_banded): arm7 at N = 128
+# SQP past the fused QP's 1536 Schur rows (the banded path, csrc/tmpc_ctx.h qp_banded): arm7 at N = 128
 # (1792 rows) with PCG-SS, arm6 at N = 256 (3072 rows) with method S; the oracle's QP in the banded path's
 # canonical order (oracle/hard.py: the dense KKT with no constraint rows, pcg_canonical)
 CBIG = [(7, 128, 1000, "PCG-SS", {}), (7, 128, 1001, "PCG-SS", {}), (6, 256, 1010, "S", {}),

@@ -33,6 +33,22 @@ def test_library_exports_every_declared_symbol():
     assert not missing, missing
 
 
+def test_library_exports_exactly_the_declared_symbols():
+    """the unmangled tmpc_* exports are the header's functions and nothing more: a helper of the entry-point
+    files that leaks out of its namespace into extern "C" shows up here"""
+    import shutil
+    import subprocess
+    from trajoptmpcreference_amd import _native
+    nm = shutil.which("nm")
+    if nm is None:
+        pytest.skip("no nm on this machine to list the library's exported symbols")
+    r = subprocess.run([nm, "-D", "--defined-only", _native.LIB_PATH], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    exported = sorted({line.split()[-1] for line in r.stdout.splitlines()
+                       if line.split() and re.fullmatch(r"tmpc_[a-z0-9_]+", line.split()[-1])})
+    assert exported == header_functions()
+
+
 def test_binding_matches_header():
     from trajoptmpcreference_amd import _native
     assert sorted(_native.SIGNATURES) == header_functions()

@@ -146,7 +146,7 @@ BIG = sorted(glob.glob(os.path.join(GOLDEN, "oracle_big_*.npz")))
 @pytest.mark.parametrize("f", BIG, ids=lambda f: os.path.basename(f))
 def test_sqp_past_the_fused_rows_matches_oracle(f):
     """Past the fused QP's 1536 Schur rows the QP takes the banded path of the hard-limit kernels with no
-    constraint rows (csrc/tmpc_api.cpp qp_banded): a 7-joint chain at N = 128 (1792 rows, PCG-SS) and arm6 at
+    constraint rows (csrc/tmpc_ctx.h qp_banded): a 7-joint chain at N = 128 (1792 rows, PCG-SS) and arm6 at
     N = 256 (3072 rows, method S: the banded direct elimination), against the oracle in that path's canonical
     order (tests/golden/oracle_big_*.npz, make_oracle_fixtures.py --only big): exit code, SQP iterations, the
     alpha path and every PCG count identical, trajectories within 1e-6; and every QP of the GPU's own run

@@ -3,7 +3,7 @@ on the host over the caller's own TrajoptCost / TrajoptPlant / TrajoptConstraint
 the GPU.
 
 The built-in plugins (QuadraticCost, UrdfCost, URDFPlant, the box limits) have device implementations and
-the whole SQP runs on the device (csrc/tmpc_api.cpp sqp_device).  A subclass that overrides one of their
+the whole SQP runs on the device (csrc/tmpc_solve.cpp sqp_device).  A subclass that overrides one of their
 hooks -- or any other TrajoptCost / TrajoptPlant subclass -- has none: its hooks are Python.  For those
 the reference's own loop runs here, calling the hooks exactly where the reference calls them
 (formKKTSystemBlocks :200-271, totalCost :296-310, totalHardConstraintViolation :273-294, the line-search
