@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-#define TMPC_ABI_VERSION 10  /* 10: tmpc_*_solve_stream_device; 9: tmpc_pcg_dense_batch; 8: tmpc_qp_blocks_batch */
+#define TMPC_ABI_VERSION 11  /* 11: tmpc_ilqr_step_batch; 10: tmpc_*_solve_stream_device; 9: tmpc_pcg_dense_batch;
+                                8: tmpc_qp_blocks_batch */
 
 /* SQPSolverMethods (TrajoptMPCReference.py:13-18). */
 #define TMPC_LINSYS_S 1      /* Schur complement, direct block-tridiagonal solve (:441-446; np.linalg.solve in the reference) */
@@ -320,6 +321,36 @@ int tmpc_fd_grad_batch(tmpc_ctx* ctx, int K, double dt, const double* x, const d
 int tmpc_qp_batch(tmpc_ctx* ctx, int B, int N, double dt, int linsys, const double* rho, const double* x,
                   const double* u, const double* xs, const double* guess, double* dxul, int32_t* pcg_iters,
                   double* S_diag, double* S_lo, double* gamma, double* P_diag);
+
+/* One iLQR iteration's sweeps for B problems (ABI 11; algorithm: oracle/ilqr.py), without the decision: what
+ * an iteration of tmpc_ilqr_solve_batch runs before its acceptance test -- the integrator Jacobians, the
+ * Riccati backward sweep and the T closed-loop trial rollouts with their costs -- through the same kernels
+ * and the same precision selection (options.precision) as a solve.  The sweeps run at the trajectory given:
+ * x [B][nx][N] is NOT replaced by a rollout of u [B][nu][N-1]; every problem is active; rho [B] is each
+ * problem's regularisation.  Outputs (host arrays, each nullable):
+ *   A [B][N-1][nx][nx], Bm [B][N-1][nx][nu]   the integrator Jacobians the backward sweep consumed;
+ *   K [B][N-1][nu][nx], d [B][N-1][nu]        feedback gains and feed-forward terms, with the sign the forward
+ *                                             sweep ADDS them: u^_k = u_k + alpha d_k + K_k (x^_k - x_k)
+ *                                             (K = -Q_uu^-1 Q_ux, d = -Q_uu^-1 Q_u);
+ *   dV [B][2]                                 (dV1, dV2) = (sum_k d_k^T Q_u, sum_k d_k^T Q_uu d_k / 2);
+ *   ok [B]                                    1 unless a pivot of some Q_uu's Cholesky factor was <= 0;
+ *   alphas [T]                                the trial step lengths;
+ *   xt [B][T][nx][N], ut [B][T][nu][N-1], Jt [B][T]   trial t's trajectory and total cost (soft values included;
+ *                                             a diverged trial's entries are non-finite).
+ * T is the length of the options' alpha schedule, 1, alpha_factor, alpha_factor^2, ... while the previous
+ * entry is > alpha_min (9 with the defaults; at most 64).  The caller passes its T, the size of its alphas /
+ * xt / ut / Jt arrays, and the call refuses a T that is not the schedule's.  For a problem with ok = 0 the
+ * K, d, dV, xt, ut and Jt rows are undefined (the sweep stopped at the failing knot and no trial ran).
+ * Fails where tmpc_ilqr_solve_batch does: UrdfCost, hard box limits, a wide model (8..12 joints) outside
+ * fp64 or with box limits.
+ * With soft box limits the sweeps carry their jacobian terms and the trial costs their values at the
+ * context's soft state (mu / lambda per knot, tmpc_set_soft_state).  That state is kept per (B, N): when the
+ * last tmpc_set_soft_state or solve was for a different B or N, it is first reset to the limits' initial
+ * constants -- so set it (tmpc_set_soft_state with this B, N) right before a tmpc_ilqr_step_batch that must
+ * see a particular mu / lambda. */
+int tmpc_ilqr_step_batch(tmpc_ctx* ctx, int B, int N, double dt, const double* x, const double* u, const double* rho,
+                         int T, double* A, double* Bm, double* K, double* d, double* dV, int32_t* ok, double* alphas,
+                         double* xt, double* ut, double* Jt);
 
 /* solveKKTSystem / solveKKTSystem_Schur (TrajoptMPCReference.py:313-455) on the blocks of formKKTSystemBlocks
  * (:118-271) as the caller's own plugin hooks formed them -- the QP of the drop-in's plugin-hook path, for

@@ -150,6 +150,58 @@ def backward(A, B, lx, lu, lxx, luu, rho, solve="canonical"):
     return K, d, dV1, dV2, True
 
 
+def backward_hp(A, B, lx, lu, lxx, luu, rho, dtype=np.longdouble):
+    """The recursion of `backward` with every array and scalar in `dtype`: the extended-precision reference
+    of the Riccati sweep (np.longdouble, the x87 80-bit format: eps 1.1e-19), and with dtype = np.float32 a
+    plain fp32 sweep.  [K | d] by a hand-written Cholesky (column j scaled by the pivot's reciprocal, as
+    chol_solve) and the two substitutions: np.linalg has no long-double path, while `@` on long-double arrays
+    runs numpy's own loops.  Returns (K [N-1][nu][nx], d [N-1][nu], dV1, dV2) in dtype, or None when a pivot
+    of some Q_uu is not positive."""
+    def cv(a):
+        return np.asarray(a, dtype=dtype)
+    N = len(lx)
+    nu = np.asarray(lu[0]).shape[0]
+    nx = np.asarray(lx[0]).shape[0]
+    one, half = dtype(1), dtype(0.5)
+    rhoI = dtype(rho) * np.eye(nu, dtype=dtype)
+    Vx = cv(lx[N - 1]).copy()
+    Vxx = cv(lxx[N - 1]).copy()
+    K = np.zeros((N - 1, nu, nx), dtype=dtype)
+    d = np.zeros((N - 1, nu), dtype=dtype)
+    dV1 = dV2 = dtype(0)
+    for k in range(N - 2, -1, -1):
+        Ak, Bk = cv(A[k]), cv(B[k])
+        Qx = cv(lx[k]) + Ak.T @ Vx
+        Qu = cv(lu[k]) + Bk.T @ Vx
+        Qxx = cv(lxx[k]) + Ak.T @ (Vxx @ Ak)
+        Quu = cv(luu[k]) + Bk.T @ (Vxx @ Bk) + rhoI
+        Qux = Bk.T @ (Vxx @ Ak)
+        L = np.zeros((nu, nu), dtype=dtype)
+        ri = np.zeros(nu, dtype=dtype)
+        for j in range(nu):
+            s = Quu[j, j] - L[j, :j] @ L[j, :j]
+            if not s > 0:
+                return None
+            L[j, j] = np.sqrt(s)
+            ri[j] = one / L[j, j]
+            for i in range(j + 1, nu):
+                L[i, j] = (Quu[i, j] - L[i, :j] @ L[j, :j]) * ri[j]
+        y = np.hstack([Qux, Qu[:, None]]).astype(dtype)
+        for i in range(nu):                       # L y = rhs
+            y[i] = (y[i] - L[i, :i] @ y[:i]) * ri[i]
+        for i in range(nu - 1, -1, -1):           # L^T z = y
+            y[i] = (y[i] - L[i + 1:, i] @ y[i + 1:]) * ri[i]
+        assert y.dtype == dtype
+        K[k] = -y[:, :-1]
+        d[k] = -y[:, -1]
+        dV1 = dV1 + d[k] @ Qu
+        dV2 = dV2 + half * (d[k] @ (Quu @ d[k]))
+        Vx = Qx + Qux.T @ d[k]
+        Vxx = Qxx + Qux.T @ K[k]
+        Vxx = half * (Vxx + Vxx.T)
+    return K, d, dV1, dV2
+
+
 def forward(model, x, u, K, d, alpha, dt):
     N = x.shape[1]
     xn = np.zeros_like(x)

@@ -87,9 +87,20 @@ static void check_band_round_trip() {
   CHECK(dev[((size_t)0 * BW + 1) * dmax + 3] == 0.0);                                            // its interior zero (column 2)
 }
 
+// two knot-major trajectories of 3 knots x 2 entries -> [2][2][3]
+static void check_knot_major_to_traj() {
+  const double km[12] = {0, 1, 10, 11, 20, 21, 100, 101, 110, 111, 120, 121};   // tag = 100 m + 10 knot + entry
+  double out[12];
+  for (double& v : out) v = -1.0;
+  tmpc::knot_major_to_traj(2, 3, 2, km, out);
+  const double want[12] = {0, 10, 20, 1, 11, 21, 100, 110, 120, 101, 111, 121};
+  for (int i = 0; i < 12; ++i) CHECK(out[i] == want[i]);
+}
+
 int main() {
   check_pack_dxul();
   check_gather();
+  check_knot_major_to_traj();
   check_band_round_trip();
   if (failures) return 1;
   printf("host pack ok\n");

@@ -53,7 +53,7 @@ def test_binding_matches_header():
     from trajoptmpcreference_amd import _native
     assert sorted(_native.SIGNATURES) == header_functions()
     lib = _native.load_library()
-    assert lib.tmpc_abi_version() == 10
+    assert lib.tmpc_abi_version() == 11
 
 
 def test_options_struct_layout_and_defaults():

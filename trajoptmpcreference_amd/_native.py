@@ -112,6 +112,8 @@ SIGNATURES = {
     "tmpc_fd_grad_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     "tmpc_qp_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip,
                                 _dp, _dp, _dp, _dp]),
+    "tmpc_ilqr_step_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp,
+                                       _dp, _dp, _ip, _dp, _dp, _dp, _dp]),
     "tmpc_qp_blocks_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp,
                                        _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp]),
     "tmpc_qp_blocks_banded_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
@@ -434,6 +436,37 @@ class Context:
                                            _ptr(Pd)),
                     "tmpc_qp_batch")
         return dict(dxul=dxul, pcg_iters=iters, S_diag=Sd, S_lo=Sl, gamma=g, P_diag=Pd)
+
+    def alpha_count(self):
+        """T, the line-search trials of the options: 1, f, f^2, ... while the previous entry is > alpha_min
+        (alpha_list, csrc/tmpc_ctx.h)."""
+        al, T = 1.0, 1
+        while al > self.options.alpha_min_SQP_DDP and T < 64:
+            al *= self.options.alpha_factor_SQP_DDP
+            T += 1
+        return T
+
+    def ilqr_step_batch(self, x, u, N, dt, rho, want_trials=True):
+        """One iLQR iteration's sweeps at the given trajectories (tmpc_ilqr_step_batch; x is not replaced by a
+        rollout): dict(A, Bm, K [B][N-1][nu][nx], d [B][N-1][nu], dV [B][2], ok [B], alphas [T], and with
+        want_trials xt [B][T][nx][N], ut [B][T][nu][N-1], Jt [B][T]).  K and d are the terms the forward sweep
+        adds; the rows of a problem with ok = 0 are undefined."""
+        x, u = _c64(x), _c64(u)
+        self._check_traj(x, u, N)
+        B, nx, _ = x.shape
+        nu = u.shape[1]
+        rho = _c64(np.broadcast_to(np.asarray(rho, dtype=np.float64), (B,)))
+        T = self.alpha_count()
+        out = dict(A=np.zeros((B, N - 1, nx, nx)), Bm=np.zeros((B, N - 1, nx, nu)), K=np.zeros((B, N - 1, nu, nx)),
+                   d=np.zeros((B, N - 1, nu)), dV=np.zeros((B, 2)), ok=np.zeros(B, dtype=np.int32),
+                   alphas=np.zeros(T))
+        if want_trials:
+            out.update(xt=np.zeros((B, T, nx, N)), ut=np.zeros((B, T, nu, N - 1)), Jt=np.zeros((B, T)))
+        self._check(self.lib.tmpc_ilqr_step_batch(
+            self.h, B, int(N), float(dt), _ptr(x), _ptr(u), _ptr(rho), T, _ptr(out["A"]), _ptr(out["Bm"]),
+            _ptr(out["K"]), _ptr(out["d"]), _ptr(out["dV"]), _ptr(out["ok"]), _ptr(out["alphas"]), _ptr(out.get("xt")),
+            _ptr(out.get("ut")), _ptr(out.get("Jt"))), "tmpc_ilqr_step_batch")
+        return out
 
     def qp_blocks_batch(self, G, g, A, Bm, c, rho, method="PCG-SS", guess=None, want_blocks=False):
         """solveKKTSystem(_Schur) on caller-formed blocks (tmpc_qp_blocks_batch, the plugin-hook QP):

@@ -1,5 +1,5 @@
-// C ABI (include/tmpc.h): the unit entry points -- dynamics, one QP, the plugin-hook QPs on caller-formed blocks
-// and the stand-alone PCG solvers.
+// C ABI (include/tmpc.h): the unit entry points -- dynamics, one QP, one iLQR iteration's sweeps, the plugin-hook
+// QPs on caller-formed blocks and the stand-alone PCG solvers.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -225,6 +225,60 @@ int tmpc_qp_batch(tmpc_ctx* ctx, int B, int N, double dt, int linsys, const doub
   if (gamma) HIP_OK(hipMemcpy(gamma, w.gam, sizeof(double) * B * N * nx, hipMemcpyDeviceToHost));
   if (P_diag && precond != PRECOND_J && precond != 0)
     HIP_OK(hipMemcpy(P_diag, w.Pd, sizeof(double) * B * N * nx * nx, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int tmpc_ilqr_step_batch(tmpc_ctx* ctx, int B, int N, double dt, const double* x, const double* u, const double* rho,
+                         int T, double* A, double* Bm, double* K, double* d, double* dV, int32_t* ok, double* alphas,
+                         double* xt, double* ut, double* Jt) {
+  if (!ctx) return -1;
+  IlqrSweep q;
+  int rc = ilqr_sweep_setup(ctx, B, N, false, q);   // what the iLQR driver refuses, its buffers and soft state
+  if (rc) return rc;
+  if (T != q.T)
+    return fail(ctx, "tmpc_ilqr_step_batch: T = %d, but the options' alpha schedule (1, alpha_factor, ... while "
+                     "alpha > alpha_min) has %d trials", T, q.T);
+  if (!rho || !x || !u) return fail(ctx, "null input");
+  hipSetDevice(ctx->device);
+  const int nj = ctx->hmodel.n, nx = 2 * nj, Kn = N - 1;
+  Work w;
+  if ((rc = alloc_work(ctx, B, N, w, false))) return rc;
+  ProbState st;
+  if ((rc = alloc_state(ctx, B, st))) return rc;
+  BUF(double, io_x, (size_t)B * nx * N);
+  BUF(double, io_u, (size_t)B * nj * Kn);
+  HIP_OK(hipMemcpyAsync(io_x, x, sizeof(double) * B * nx * N, hipMemcpyHostToDevice, ctx->stream));
+  HIP_OK(hipMemcpyAsync(io_u, u, sizeof(double) * B * nj * Kn, hipMemcpyHostToDevice, ctx->stream));
+  HIP_OK(hipMemcpyAsync(st.rho, rho, sizeof(double) * B, hipMemcpyHostToDevice, ctx->stream));
+  ProbState st0 = st;   // the initial state of a solve (every problem active), but for rho: the caller's
+  st0.rho = st.drho;
+  launch_init_state(ctx->stream, B, 0.0, st0, nullptr);
+  HIP_OK(hipGetLastError());
+  // xs = x[:, 0]: the trajectory is taken as given (no rollout), so the defects run_dynamics also forms are unused
+  HIP_OK(hipMemcpy2DAsync(w.xs, sizeof(double), io_x, (size_t)N * sizeof(double), sizeof(double), (size_t)B * nx,
+                          hipMemcpyDeviceToDevice, ctx->stream));
+  if ((rc = ilqr_sweeps(ctx, N, dt, io_x, io_u, st, w, PList{nullptr, nullptr}, B, q))) return rc;
+  HIP_OK(hipStreamSynchronize(ctx->stream));
+  resolve_timings(ctx);
+  if (A) HIP_OK(hipMemcpy(A, w.A, sizeof(double) * B * Kn * nx * nx, hipMemcpyDeviceToHost));
+  if (Bm) HIP_OK(hipMemcpy(Bm, w.Bm, sizeof(double) * B * Kn * nx * nj, hipMemcpyDeviceToHost));
+  if (K) HIP_OK(hipMemcpy(K, q.K, sizeof(double) * B * Kn * nj * nx, hipMemcpyDeviceToHost));
+  if (d) HIP_OK(hipMemcpy(d, q.d, sizeof(double) * B * Kn * nj, hipMemcpyDeviceToHost));
+  if (dV) HIP_OK(hipMemcpy(dV, q.dV, sizeof(double) * B * 2, hipMemcpyDeviceToHost));
+  if (ok) HIP_OK(hipMemcpy(ok, q.ok, sizeof(int) * B, hipMemcpyDeviceToHost));
+  if (alphas) HIP_OK(hipMemcpy(alphas, q.alphas, sizeof(double) * T, hipMemcpyDeviceToHost));
+  if (Jt) HIP_OK(hipMemcpy(Jt, q.J, sizeof(double) * B * T, hipMemcpyDeviceToHost));
+  // the trials are knot-major on the device ([B][T][N][nx]): the caller's are the trajectory layout [nx][N]
+  if (xt) {
+    std::vector<double> h((size_t)B * T * N * nx);
+    HIP_OK(hipMemcpy(h.data(), q.xt, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    knot_major_to_traj(B * T, N, nx, h.data(), xt);
+  }
+  if (ut) {
+    std::vector<double> h((size_t)B * T * Kn * nj);
+    HIP_OK(hipMemcpy(h.data(), q.ut, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    knot_major_to_traj(B * T, Kn, nj, h.data(), ut);
+  }
   return 0;
 }
 

@@ -285,6 +285,25 @@ int run_qp(tmpc_ctx* ctx, int B, int N, double dt, int precond, const double* d_
            const ProbState& st, Work& w, bool keep_blocks, PList P, int nb);
 int sqp_device(tmpc_ctx* ctx, int B, int N, double dt, int linsys, double* d_x, double* d_u, TraceDev* tr_out,
                bool keep_warm = false, bool hard_trace = false, const StreamDev* sd = nullptr);
+// One iLQR iteration's sweeps (shared by the iLQR driver and tmpc_ilqr_step_batch): what the backward sweep
+// leaves for the forward one and the T trials' rollouts and costs for the decision.  Trials are knot-major
+// ([B][T][N][nx], [B][T][N-1][nu]: tmpc_ilqr.hip).
+struct IlqrSweep {
+  int T;                       // line-search trials, alpha_list of the options
+  double *alphas;              // [T]
+  double *K, *d, *dV;          // [B][N-1][nu][nx], [B][N-1][nu], [B][2]
+  int* ok;                     // [B]
+  double *xt, *ut, *J;         // [B][T][N][nx], [B][T][N-1][nu], [B][T]
+  double *jac;                 // soft limits: the knots' jacobians [B][N][3 n] (else null)
+  double *smu, *slam, *sphi;   // soft limits: the context's state the sweeps run on (else null)
+};
+// What iLQR refuses (UrdfCost, hard limits, check_ready's wide-model restrictions), then the sweeps' buffers, the
+// soft state (init_soft; fresh: from the limits' initial constants regardless) and the alphas on the stream.
+int ilqr_sweep_setup(tmpc_ctx* ctx, int B, int N, bool fresh_soft, IlqrSweep& q);
+// run_dynamics, the backward sweep, the T rollouts with their costs (soft values included): the problems of
+// P / nb that are st.active, at st.rho
+int ilqr_sweeps(tmpc_ctx* ctx, int N, double dt, const double* d_x, const double* d_u, const ProbState& st,
+                const Work& w, PList P, int nb, const IlqrSweep& q);
 int ilqr_device(tmpc_ctx* ctx, int B, int N, double dt, double* d_x, double* d_u, TraceDev* tr_out,
                 const StreamDev* sd = nullptr);
 int stream_solve(tmpc_ctx* ctx, int N, double dt, int linsys, const tmpc_stream* s);

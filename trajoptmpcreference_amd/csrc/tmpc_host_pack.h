@@ -33,6 +33,15 @@ inline void gather_dyn_lambda(int B, int N, int nx, int dmax, const int* roff, c
         out[((size_t)b * N + k) * nx + i] = lam_band[(size_t)b * dmax + roff[(size_t)b * N + k] + i];
 }
 
+// M knot-major trajectories [M][n_knots][w] (the iLQR trials on the device) in the trajectory layout of the
+// ABI, [M][w][n_knots] (x [nx][N], u [nu][N-1]).
+inline void knot_major_to_traj(int M, int n_knots, int w, const double* km, double* traj) {
+  for (int m = 0; m < M; ++m)
+    for (int k = 0; k < n_knots; ++k)
+      for (int i = 0; i < w; ++i)
+        traj[((size_t)m * w + i) * n_knots + k] = km[((size_t)m * n_knots + k) * w + i];
+}
+
 // The two layouts of a banded S (half-width W, dmax rows, dim[b] <= dmax of them used):
 //   ABI    row-major [B][dmax][2W+1]: entry o of row a is column a - W + o
 //   device row-start-relative [B][2W+1][dmax]: entry j of row a is column rng[a][0] + j (tmpc_hard.hip), with

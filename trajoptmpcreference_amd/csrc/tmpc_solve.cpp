@@ -629,24 +629,15 @@ int sqp_device(tmpc_ctx* ctx, int B, int N, double dt, int linsys, double* d_x, 
 }
 
 // ------------------------------------------------------------------ iLQR driver (oracle/ilqr.py)
-int ilqr_device(tmpc_ctx* ctx, int B, int N, double dt, double* d_x, double* d_u, TraceDev* tr_out,
-                const StreamDev* sd) {
+int ilqr_sweep_setup(tmpc_ctx* ctx, int B, int N, bool fresh_soft, IlqrSweep& q) {
   int rc = check_ready(ctx, B, N, false);
   if (rc) return rc;
   if (ctx->hcost.kind != COST_QUADRATIC) return fail(ctx, "iLQR supports QuadraticCost only (UrdfCost: use SQP)");
   if (ctx->hlim.any_hard)
     return fail(ctx, "iLQR has no constraint rows: hard box constraints (ACTIVE_SET / FULL_SET) need SQP");
   const int nj = ctx->hmodel.n, nx = 2 * nj, K = N - 1;
-  const bool chain = ctx->hmodel.chain != 0;
-  const tmpc_options& o = ctx->opts;
-  const SolverOpts so = solver_opts(o);
-  const std::vector<double> al = alpha_list(o);
+  const std::vector<double> al = alpha_list(ctx->opts);
   const int T = (int)al.size();
-  Outer L{};
-  if ((rc = outer_alloc(ctx, B, N, false, sd != nullptr, L))) return rc;
-  const Work& w = L.w;
-  const ProbState& st = L.st;
-  const AliveList& alv = L.alv;
   BUF(double, alphas, T);
   BUF(double, il_K, (size_t)B * K * nj * nx);
   BUF(double, il_d, (size_t)B * K * nj);
@@ -655,19 +646,61 @@ int ilqr_device(tmpc_ctx* ctx, int B, int N, double dt, double* d_x, double* d_u
   BUF(double, il_xt, (size_t)B * T * nx * N);
   BUF(double, il_ut, (size_t)B * T * nj * K);
   BUF(double, il_J, (size_t)B * T);
+  q = IlqrSweep{};
+  q.T = T; q.alphas = alphas; q.K = il_K; q.d = il_d; q.dV = il_dV; q.ok = il_ok; q.xt = il_xt; q.ut = il_ut;
+  q.J = il_J;
+  if (ctx->hlim.any) {
+    if ((rc = init_soft(ctx, B, N, fresh_soft, nullptr))) return rc;
+    q.smu = ctx->soft_mu;
+    q.slam = ctx->soft_lam;
+    q.sphi = ctx->soft_phi;
+    BUF(double, il_jac_buf, (size_t)B * N * 3 * nj);   // soft-limit jacobians of every knot (Riccati sweep)
+    q.jac = il_jac_buf;
+  }
+  HIP_OK(hipMemcpyAsync(alphas, al.data(), al.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  return 0;
+}
+
+int ilqr_sweeps(tmpc_ctx* ctx, int N, double dt, const double* d_x, const double* d_u, const ProbState& st,
+                const Work& w, PList P, int nb, const IlqrSweep& q) {
+  const int nj = ctx->hmodel.n;
+  const bool chain = ctx->hmodel.chain != 0;
+  if (int r = run_dynamics(ctx, N, dt, d_x, d_u, st, w, P, nb)) return r;
+  {
+    Timed t(ctx, "ilqr_backward");
+    LAUNCH_OK(launch_ilqr_backward(ric32(ctx), ctx->stream, nj, ctx->dcost, ctx->dlim, P, nb, N, d_x, d_u, st.rho,
+                                   st.active, w.A, w.Bm, q.smu, q.slam, q.jac, q.K, q.d, q.dV, q.ok));
+  }
+  {
+    Timed t(ctx, "ilqr_forward");
+    LAUNCH_OK(launch_ilqr_forward(val32(ctx), ctx->stream, nj, chain, ctx->model_id, ctx->dmodel, ctx->dcost, ctx->dlim,
+                                  q.smu, q.slam, P, nb, N, q.T, dt, 0, q.alphas, d_x, d_u, q.K, q.d, st.active, q.ok,
+                                  q.xt, q.ut, q.J));
+  }
+  return 0;
+}
+
+int ilqr_device(tmpc_ctx* ctx, int B, int N, double dt, double* d_x, double* d_u, TraceDev* tr_out,
+                const StreamDev* sd) {
+  IlqrSweep q;
+  int rc = ilqr_sweep_setup(ctx, B, N, sd != nullptr, q);   // a stream's problems start from the initial constants
+  if (rc) return rc;
+  const int nj = ctx->hmodel.n, nx = 2 * nj;
+  const bool chain = ctx->hmodel.chain != 0;
+  const tmpc_options& o = ctx->opts;
+  const SolverOpts so = solver_opts(o);
+  const int T = q.T;
+  Outer L{};
+  if ((rc = outer_alloc(ctx, B, N, false, sd != nullptr, L))) return rc;
+  const Work& w = L.w;
+  const ProbState& st = L.st;
+  const AliveList& alv = L.alv;
   BUF(unsigned long long, il_prob_counters, (size_t)B * 3);   // per-problem tallies of k_ilqr_decide
   HIP_OK(hipMemsetAsync(L.counters, 0, 4 * sizeof(unsigned long long), ctx->stream));
   HIP_OK(hipMemsetAsync(il_prob_counters, 0, (size_t)B * 3 * sizeof(unsigned long long), ctx->stream));
-  double* il_jac = nullptr;
-  if (L.soft) {
-    if ((rc = init_soft(ctx, B, N, sd != nullptr, nullptr))) return rc;
-    L.smu = ctx->soft_mu;
-    L.slam = ctx->soft_lam;
-    L.sphi = ctx->soft_phi;
-    BUF(double, il_jac_buf, (size_t)B * N * 3 * nj);   // soft-limit jacobians of every knot (Riccati sweep)
-    il_jac = il_jac_buf;
-  }
-  HIP_OK(hipMemcpyAsync(alphas, al.data(), al.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  L.smu = q.smu;
+  L.slam = q.slam;
+  L.sphi = q.sphi;
   StreamDev sdr{};
   if (sd) {
     // a stream's problems start from the rollout of u from x[:, 0] too: roll the `period` inputs out once
@@ -691,29 +724,17 @@ int ilqr_device(tmpc_ctx* ctx, int B, int N, double dt, double* d_x, double* d_u
     ProbState sti = st;
     sti.active = mask;
     LAUNCH_OK(launch_ilqr_init_cost(ctx->stream, nj, ctx->dcost, ctx->dlim, L.smu, L.slam, alv.P, alv.nb, N, d_x, d_u,
-                                    mask, il_J));
-    launch_ilqr_decide(ctx->stream, alv.P, alv.nb, N, nx, nj, 1, 1, alphas, so, il_J, il_dV, il_ok, il_xt, il_ut, d_x, d_u, sti,
-                       L.tr, ac, nullptr, activate);
+                                    mask, q.J));
+    launch_ilqr_decide(ctx->stream, alv.P, alv.nb, N, nx, nj, 1, 1, q.alphas, so, q.J, q.dV, q.ok, q.xt, q.ut, d_x, d_u,
+                       sti, L.tr, ac, nullptr, activate);
     HIP_OK(hipGetLastError());
     return 0;
   };
   auto ilqr_iteration = [&](int* ac) -> int {
-    if (int r = run_dynamics(ctx, N, dt, d_x, d_u, st, w, alv.P, alv.nb)) return r;
-    {
-      Timed t(ctx, "ilqr_backward");
-      LAUNCH_OK(launch_ilqr_backward(ric32(ctx), ctx->stream, nj, ctx->dcost, ctx->dlim, alv.P, alv.nb, N, d_x, d_u,
-                                     st.rho, st.active,
-                                     w.A, w.Bm, L.smu, L.slam, il_jac, il_K, il_d, il_dV, il_ok));
-    }
-    {
-      Timed t(ctx, "ilqr_forward");
-      LAUNCH_OK(launch_ilqr_forward(val32(ctx), ctx->stream, nj, chain, ctx->model_id, ctx->dmodel, ctx->dcost, ctx->dlim, L.smu,
-                                    L.slam, alv.P, alv.nb, N, T, dt, 0, alphas, d_x, d_u, il_K, il_d, st.active, il_ok, il_xt, il_ut,
-                                    il_J));
-    }
+    if (int r = ilqr_sweeps(ctx, N, dt, d_x, d_u, st, w, alv.P, alv.nb, q)) return r;
     Timed t(ctx, "ilqr_decide");
-    launch_ilqr_decide(ctx->stream, alv.P, alv.nb, N, nx, nj, T, 0, alphas, so, il_J, il_dV, il_ok, il_xt, il_ut, d_x, d_u, st, L.tr,
-                       ac, il_prob_counters);
+    launch_ilqr_decide(ctx->stream, alv.P, alv.nb, N, nx, nj, T, 0, q.alphas, so, q.J, q.dV, q.ok, q.xt, q.ut, d_x, d_u,
+                       st, L.tr, ac, il_prob_counters);
     HIP_OK(hipGetLastError());
     return 0;
   };
