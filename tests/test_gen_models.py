@@ -1,7 +1,7 @@
 """tools/gen_models.py --urdf: a robot outside the bundled arms gets compile-time tables (GRiD's per-robot
 codegen) -- here a branched 4-joint tree with a prismatic joint.  The generated header must
-carry the robot's tables with its topology (chain = 0), its exact-match test and a dispatch case with the
-general-topology instantiation, and must compile (hipcc -fsyntax-only on a unit that includes it)."""
+carry the robot's tables with its topology (chain = 0), its exact-match test and its entry in the dispatch's
+model list (which selects the general-topology instantiation from chain = 0), and must compile (hipcc -fsyntax-only on a unit that includes it)."""
 import os
 import shutil
 import subprocess
@@ -33,7 +33,7 @@ def test_user_urdf_gets_compiled_tables(tmp_path):
     h = out.read_text()
     assert "struct Robot8 {" in h and "static constexpr int chain = 0;" in h and "branched" in h
     assert "if (same_model<Robot8>(m)) return Robot8::ID;" in h
-    assert "case Robot8::ID: LAUNCH<Robot8::n, (Robot8::chain != 0), Robot8>::CALL;" in h
+    assert "using StaticModels = ModelList<Arm1, Arm2, Arm3, Arm4, Arm5, Arm6, Arm7, Robot8>;" in h
     # the bundled tables are unchanged
     bundled = open(os.path.join(ROOT, "trajoptmpcreference_amd", "csrc", "tmpc_models.h")).read()
     assert h.startswith(bundled.split("// exact field-by-field")[0].rstrip())
@@ -41,7 +41,9 @@ def test_user_urdf_gets_compiled_tables(tmp_path):
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
     unit = tmp_path / "unit.hip"
-    unit.write_text('#include "tmpc_models.h"\nint probe(const tmpc::ModelDev& m) { return tmpc::match_static_model(m); }\n')
+    unit.write_text('#include "tmpc_models.h"\nint probe(const tmpc::ModelDev& m) { return tmpc::match_static_model(m); }\n'
+                    'int route(int mid, int nj, bool chain) {\n  int n = 0;\n'
+                    '  return tmpc::dispatch_model(mid, nj, chain, [&](auto t) { n += decltype(t)::nj; }) + n;\n}\n')
     r = subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-I", str(tmp_path), "-I",
                         os.path.join(ROOT, "trajoptmpcreference_amd", "csrc"), str(unit)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -452,7 +452,8 @@ def _hard_pcg_bytes(Ss, iters, nx, ptype, dmax):
     stair) less those the kernel keeps in LDS -- as many as fit in the 160 KB after its vectors, diagonal
     blocks first (tmpc_hard.hip hard_pcg_cache_offset)."""
     slots = -(-dmax // 1024)
-    # tmpc_hard.hip hard_pcg_reg_diag (slot 0, in registers; TMPC_HARD_REG, a build constant)
+    # tmpc_hard.hip hard_pcg_reg_diag (slot 0, in registers; HARD_REG, a constexpr there: the TMPC_HARD_REG
+    # build switch it was tuned with no longer exists, the comment above the constant records the outcome)
     reg = int(os.environ.get("TMPC_TEST_HARD_REG", "24"))
     REG = (16 if nx <= 4 else (reg - 4 if nx >= 14 or nx == 8 else reg)) - (8 if slots >= 3 else 0)
     tot = 0.0

@@ -349,21 +349,14 @@ __global__ void __launch_bounds__(64) k_mpc_shift(MT M, int B, int N, double dt,
   }
 }
 
-#define TMPC_GRID(n, bs) dim3(((n) + (bs) - 1) / (bs)), dim3(bs)
-
 template <int NJ, bool CHAIN, class MT>
 struct LaunchFD {
   static void qp_fd(bool f32, hipStream_t s, const ModelDev* M, PList P, int B, int N, double dt, const double* x,
                     const double* u, const double* xs, const int* need, double* qdd, double* cvec) {
-    if constexpr (!kWide<NJ>) {   // fp32 instances for up to NJ_FULL joints only
-      if (f32) {
-        hipLaunchKernelGGL((k_qp_fd<NJ, CHAIN, MT, float>), TMPC_GRID(B * (N - 1), 256), 0, s, MT::make(M), P, B, N, dt, x, u,
-                           xs, need, qdd, cvec);
-        return;
-      }
-    }
-    hipLaunchKernelGGL((k_qp_fd<NJ, CHAIN, MT, double>), TMPC_GRID(B * (N - 1), 256), 0, s, MT::make(M), P, B, N, dt, x, u,
-                       xs, need, qdd, cvec);
+    with_real<NJ>(f32, [&](auto r) {
+      hipLaunchKernelGGL((k_qp_fd<NJ, CHAIN, MT, decltype(r)>), TMPC_GRID(B * (N - 1), 256), 0, s, MT::make(M), P, B, N, dt,
+                         x, u, xs, need, qdd, cvec);
+    });
   }
   // a runtime model (ModelRef) takes the general-topology line-search instance even for a chain: with
   // runtime coefficients the chain specialisation's unrolled recursion spills 9x more (k_ls_terms<6,
@@ -387,13 +380,10 @@ struct LaunchFD {
   }
   static void unit_fd(bool f32, hipStream_t s, const ModelDev* M, int K, double dt, const double* x, const double* u,
                       double* xnext, double* qdd) {
-    if constexpr (!kWide<NJ>) {   // fp32 instances for up to NJ_FULL joints only
-      if (f32) {
-        hipLaunchKernelGGL((k_unit_fd<NJ, CHAIN, MT, float>), TMPC_GRID(K, 256), 0, s, MT::make(M), K, dt, x, u, xnext, qdd);
-        return;
-      }
-    }
-    hipLaunchKernelGGL((k_unit_fd<NJ, CHAIN, MT, double>), TMPC_GRID(K, 256), 0, s, MT::make(M), K, dt, x, u, xnext, qdd);
+    with_real<NJ>(f32, [&](auto r) {
+      hipLaunchKernelGGL((k_unit_fd<NJ, CHAIN, MT, decltype(r)>), TMPC_GRID(K, 256), 0, s, MT::make(M), K, dt, x, u, xnext,
+                         qdd);
+    });
   }
   static void mpc_shift(hipStream_t s, const ModelDev* M, int B, int N, double dt, int step, int steps, double* x,
                         double* u, double* xe, double* ue) {
@@ -402,59 +392,52 @@ struct LaunchFD {
   }
   static void rollout(bool f32, hipStream_t s, const ModelDev* M, int B, int N, double dt, double* x, const double* u,
                       PList P, const int* mask) {
-    if constexpr (!kWide<NJ>) {   // fp32 instances for up to NJ_FULL joints only
-      if (f32) {
-        hipLaunchKernelGGL((k_rollout<NJ, CHAIN, MT, float>), TMPC_GRID(B, 64), 0, s, MT::make(M), P, B, N, dt, x, u, mask);
-        return;
-      }
-    }
-    hipLaunchKernelGGL((k_rollout<NJ, CHAIN, MT, double>), TMPC_GRID(B, 64), 0, s, MT::make(M), P, B, N, dt, x, u, mask);
+    with_real<NJ>(f32, [&](auto r) {
+      hipLaunchKernelGGL((k_rollout<NJ, CHAIN, MT, decltype(r)>), TMPC_GRID(B, 64), 0, s, MT::make(M), P, B, N, dt, x, u,
+                         mask);
+    });
   }
 };
-
-// dispatch tables over the joint count and the chain specialisation
-#define TMPC_DISPATCH_NJ(nj, chain, CALL)                                                              \
-  switch (mid) {                                                                                       \
-    TMPC_STATIC_MODEL_CASES(LaunchFD, CALL)                                                            \
-    default: break;                                                                                    \
-  }                                                                                                    \
-  switch (nj) {                                                                                        \
-    case 1: if (chain) LaunchFD<1, true, ModelRef>::CALL; else LaunchFD<1, false, ModelRef>::CALL; break;  \
-    case 2: if (chain) LaunchFD<2, true, ModelRef>::CALL; else LaunchFD<2, false, ModelRef>::CALL; break;  \
-    case 3: if (chain) LaunchFD<3, true, ModelRef>::CALL; else LaunchFD<3, false, ModelRef>::CALL; break;  \
-    case 4: if (chain) LaunchFD<4, true, ModelRef>::CALL; else LaunchFD<4, false, ModelRef>::CALL; break;  \
-    case 5: if (chain) LaunchFD<5, true, ModelRef>::CALL; else LaunchFD<5, false, ModelRef>::CALL; break;  \
-    case 6: if (chain) LaunchFD<6, true, ModelRef>::CALL; else LaunchFD<6, false, ModelRef>::CALL; break;  \
-    case 7: if (chain) LaunchFD<7, true, ModelRef>::CALL; else LaunchFD<7, false, ModelRef>::CALL; break;  \
-    TMPC_WIDE_CASES(LaunchFD, CALL)                                                                    \
-    default: return -2;                                                                                \
-  }                                                                                                    \
-  return 0;
 
 int launch_qp_fd(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, PList P, int B, int N,
                  double dt, const double* x, const double* u, const double* xs, const int* need, double* qdd,
                  double* cvec) {
-  TMPC_DISPATCH_NJ(nj, chain, qp_fd(f32, s, M, P, B, N, dt, x, u, xs, need, qdd, cvec))
+  return dispatch_model(mid, nj, chain, [&](auto t) {
+    using T = decltype(t);
+    LaunchFD<T::nj, T::chain, typename T::model>::qp_fd(f32, s, M, P, B, N, dt, x, u, xs, need, qdd, cvec);
+  });
 }
 int launch_ls_terms(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, const CostDev* C,
                     const ConstrDev* Cs, const double* mu, const double* lam, PList P, int B, int N, int T, double dt,
                     const double* alphas, const double* x, const double* u, const double* xs, const double* dx,
                     const double* du, const int* active, double* terms) {
-  TMPC_DISPATCH_NJ(nj, chain, ls_terms(f32, s, M, C, Cs, mu, lam, P, B, N, T, dt, alphas, x, u, xs, dx, du, active,
-                                       terms))
+  return dispatch_model(mid, nj, chain, [&](auto t) {
+    using Tag = decltype(t);
+    LaunchFD<Tag::nj, Tag::chain, typename Tag::model>::ls_terms(f32, s, M, C, Cs, mu, lam, P, B, N, T, dt, alphas, x, u,
+                                                                 xs, dx, du, active, terms);
+  });
 }
 int launch_unit_fd(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, int K, double dt,
                    const double* x, const double* u, double* xnext, double* qdd) {
-  TMPC_DISPATCH_NJ(nj, chain, unit_fd(f32, s, M, K, dt, x, u, xnext, qdd))
+  return dispatch_model(mid, nj, chain, [&](auto t) {
+    using T = decltype(t);
+    LaunchFD<T::nj, T::chain, typename T::model>::unit_fd(f32, s, M, K, dt, x, u, xnext, qdd);
+  });
 }
 int launch_rollout(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, int B, int N, double dt,
                    double* x, const double* u, PList P, const int* mask) {
-  TMPC_DISPATCH_NJ(nj, chain, rollout(f32, s, M, B, N, dt, x, u, P, mask))
+  return dispatch_model(mid, nj, chain, [&](auto t) {
+    using T = decltype(t);
+    LaunchFD<T::nj, T::chain, typename T::model>::rollout(f32, s, M, B, N, dt, x, u, P, mask);
+  });
 }
 
 int launch_mpc_shift(hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, int B, int N, double dt, int step,
                      int steps, double* x, double* u, double* xe, double* ue) {
-  TMPC_DISPATCH_NJ(nj, chain, mpc_shift(s, M, B, N, dt, step, steps, x, u, xe, ue))
+  return dispatch_model(mid, nj, chain, [&](auto t) {
+    using T = decltype(t);
+    LaunchFD<T::nj, T::chain, typename T::model>::mpc_shift(s, M, B, N, dt, step, steps, x, u, xe, ue);
+  });
 }
 
 }  // namespace tmpc

@@ -252,28 +252,16 @@ __device__ __forceinline__ int piece_unit(int kind, int knot, int idx, int p, co
 
 // S band and gamma.  Phase 1: per row and piece, Y = Ghat cf (global scratch [dmax][2][NXU] per
 // problem); phase 2: S_ab = -sum over shared knots cf_a . Y_b, gamma_a = c_a - sum_p Y_a . g.
-#ifndef TMPC_SCHUR_WPE
-#define TMPC_SCHUR_WPE 1
-#endif
 // S entries per step of k_hard_schur's phase 2 (their Y loads in flight together): 2 (four measured the
 // same at NJ = 6, profiles/r05/hard/probe_r05s.txt, at 254 VGPRs)
-#ifndef TMPC_SCHUR_EPS
-#define TMPC_SCHUR_EPS 2
-#endif
-// Y scratch layout: 1 (shipped) [2][NXU][dmax], a wave's rows consecutive: phase 1's writes coalesce
-// (row-major [dmax][2][NXU], 0: Y 84k -> 63k cycles per problem, hard_schur 0.48 -> 0.43 ms per launch at
+constexpr int SCHUR_EPS = 2;
+// Y scratch layout: [2][NXU][dmax], a wave's rows consecutive: phase 1's writes coalesce (against row-major
+// [dmax][2][NXU]: Y 84k -> 63k cycles per problem, hard_schur 0.48 -> 0.43 ms per launch at
 // B = 4096, profiles/r05/hard/probe_r05z.txt; while phase 2 read a full Y row per entry and piece the
 // row-major layout was the faster one, probe_r05w_ytransposed_rejected.txt)
-#ifndef TMPC_SCHUR_YT
-#define TMPC_SCHUR_YT 1
-#endif
-#if TMPC_SCHUR_YT
 #define Y_AT(row, q, m) Yb[((size_t)(q) * NXU + (m)) * dmax + (row)]
-#else
-#define Y_AT(row, q, m) Yb[((size_t)(row) * 2 + (q)) * NXU + (m)]
-#endif
 template <int NJ>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_SCHUR_WPE))) k_hard_schur(const CostDev* __restrict__ C, int B, int N, int W, int dmax,
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) k_hard_schur(const CostDev* __restrict__ C, int B, int N, int W, int dmax,
                                                     int rmax, const int* __restrict__ active,
                                                     const double* __restrict__ Ghat, int per_knot,
                                                     const double* __restrict__ Aall, const double* __restrict__ Ball,
@@ -286,7 +274,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_S
                                                     double* __restrict__ Y, int* __restrict__ PK,
                                                     double* __restrict__ Sb, double* __restrict__ gam,
                                                     int* __restrict__ rng, const double* __restrict__ gvec) {
-#if TMPC_HX_STAMPS
+#ifdef TMPC_HX_STAMPS
   unsigned long long sc_[4] = {}, sc_prev_ = __builtin_amdgcn_s_memtime();
 #define HS_STAMP(i_) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); sc_[i_] += n_ - sc_prev_; sc_prev_ = n_; }
 #else
@@ -349,7 +337,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_S
         // y = Ghat_kp cf (terminal knot: x block only), written out row by row, and s = y . g in the
         // same order; the row loops stay rolled so one Ghat row's loads are live at a time
         double* yo = &Y_AT(a, p, 0);
-        const size_t ys = TMPC_SCHUR_YT ? (size_t)dmax : 1;   // the stride of the entries
+        const size_t ys = dmax;   // the stride of the entries
         const double* gk = s_grad + kp * NXU;
         const auto Gx = gx_of(kp);
         double s = 0.0;
@@ -395,7 +383,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_S
         s_pk[a * 2 + p] = pk_pack(kp, uc, uv);
         if (kp < 0) continue;
         double* yo = &Y_AT(a, p, 0);
-        const size_t ys = TMPC_SCHUR_YT ? (size_t)dmax : 1;
+        const size_t ys = dmax;
         const double* gk = s_grad + kp * NXU;
         glb_cdouble* G = glb_ptr(Gf + (size_t)kp * NXU * NXU);
         const int m = kp < K ? NXU : NX;
@@ -494,7 +482,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_S
     // dependent HBM round trip kept one Y vector in flight per lane); S_ac = -(sum over the pieces p of a,
     // in order, of cf_ap . Y_cq for the piece q of c on a's knot kp_p), zero past the row up to the wave's
     // longest row (k_hard_pcg's products read it: exact zeros)
-    constexpr int EPS = TMPC_SCHUR_EPS;
+    constexpr int EPS = SCHUR_EPS;
     const int lo_a = own ? rb[2 * a] : 0;
     for (int o = l; o <= h; o += EPS) {
       bool in[EPS];
@@ -563,7 +551,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_S
     }
   }
   HS_STAMP(3);
-#if TMPC_HX_STAMPS
+#ifdef TMPC_HX_STAMPS
   if (b == 0 && (threadIdx.x & 63) == 0)
     printf("hs_stamps wave %d D %d: grad %llu Y %llu ranges %llu S %llu\n", (int)(threadIdx.x >> 6), D, sc_[0], sc_[1],
            sc_[2], sc_[3]);
@@ -572,28 +560,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_S
 #undef Y_AT
 }
 
-#ifndef TMPC_HX_NOSTREAM
-#define TMPC_HX_NOSTREAM 0
-#endif
-#ifndef TMPC_HX_NOPREC
-#define TMPC_HX_NOPREC 0
-#endif
-#ifndef TMPC_HX_STAMPS
-#define TMPC_HX_STAMPS 0
-#endif
-
 // band entries of each slot-0 row (its first ones) k_hard_pcg holds in registers for the whole solve:
 // 24 (48 VGPRs of its 128); fewer where that spills (nx = 8, 14: 20; nx = 2, 4: 16; 8 fewer in the three- and
 // four-slot instances, which hold x of three / four rows)
-#ifndef TMPC_HARD_REG
-#define TMPC_HARD_REG 24
-#endif
+constexpr int HARD_REG = 24;
 // streamed band entries per batch of loads in k_hard_pcg's product
-#ifndef TMPC_HARD_U
-#define TMPC_HARD_U 8
-#endif
+constexpr int HARD_U = 8;
 __host__ __device__ constexpr int hard_pcg_reg_diag(int nx, int slots) {
-  return (nx <= 4 ? 16 : (nx >= 14 || nx == 8 ? TMPC_HARD_REG - 4 : TMPC_HARD_REG)) - (slots >= 3 ? 8 : 0);
+  return (nx <= 4 ? 16 : (nx >= 14 || nx == 8 ? HARD_REG - 4 : HARD_REG)) - (slots >= 3 ? 8 : 0);
 }
 
 // doubles of LDS k_hard_pcg uses before its reduction slots: r and p of dmax rows, z and S p of the rows
@@ -622,11 +596,7 @@ __host__ __device__ constexpr int hard_pcg_cache_offset(int D, int nx, int slots
 // VALU: permlane swaps (32, 16), DPP row_ror:8, row_shl:4 / row_shr:4 picked by lane bit 2, quad_perm
 // (2, 1).  Each step adds the same two values as the shuffle form (addition commutes), so the sums
 // are bitwise those of __shfl_xor, without its six ds_bpermute round trips through the LDS unit.
-#ifndef TMPC_HARD_DPP
-#define TMPC_HARD_DPP 1
-#endif
 __device__ __forceinline__ double h_wave_butterfly(double v) {
-#if TMPC_HARD_DPP
   v = perm_pair_sum32(v);
   v = perm_pair_sum16(v);
   v += dpp_get<0x128, 0xf>(v);   // row_ror:8: lane l reads l ^ 8
@@ -637,9 +607,6 @@ __device__ __forceinline__ double h_wave_butterfly(double v) {
   }
   v += dpp_get<0x4E, 0xf>(v);    // quad_perm [2,3,0,1]: l ^ 2
   v += dpp_get<0xB1, 0xf>(v);    // quad_perm [1,0,3,2]: l ^ 1
-#else
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-#endif
   return v;
 }
 
@@ -755,7 +722,7 @@ __global__ void __launch_bounds__(HARD_PCG_THREADS) k_hard_pcg(int B, int W, int
   constexpr int REG = hard_pcg_reg_diag(NX, SLOTS);
   const int b = blockIdx.x;
   if (!active[b]) return;
-#if TMPC_HX_STAMPS
+#ifdef TMPC_HX_STAMPS
   unsigned long long su_[8] = {}, su_prev_ = __builtin_amdgcn_s_memtime();
 #define HX_SETUP(i_) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); su_[i_] += n_ - su_prev_; su_prev_ = n_; }
 #else
@@ -944,7 +911,7 @@ __global__ void __launch_bounds__(HARD_PCG_THREADS) k_hard_pcg(int B, int W, int
   HX_SETUP(1);
   // z = P^-1 r for row a (r read from LDS)
   auto apply_P = [&](int a) -> double {
-    if (precond == PRECOND_NONE || TMPC_HX_NOPREC) return rv[a];
+    if (precond == PRECOND_NONE) return rv[a];
     if (precond == PRECOND_J) return (1.0 / band_at(S, rg, dmax, a, a)) * rv[a];
     if (a >= nb * NX) return 0.0;   // rows past the last full block: not preconditioned (PCG.py:182)
     const int k = a / NX, i = a - k * NX;
@@ -977,7 +944,7 @@ __global__ void __launch_bounds__(HARD_PCG_THREADS) k_hard_pcg(int B, int W, int
   auto spmv = [&](int a, bool own, int jmax, int c0hi, bool cached, const double (&vc)[REG])
       -> double {
     const int c0 = c0hi >> 16;
-    constexpr int U = TMPC_HARD_U;
+    constexpr int U = HARD_U;
     double s = 0.0;
     const double* Sa = S + (own ? a : 0);
     // The streamed entries (past the register-held ones, up to the wave's longest row; the band is zero
@@ -996,9 +963,6 @@ __global__ void __launch_bounds__(HARD_PCG_THREADS) k_hard_pcg(int B, int W, int
       // (A branch per entry kept one LDS read in flight per wave.)
 #pragma unroll
       for (int u = 0; u < REG; ++u) s = s + vc[u] * pv[c0 + u];
-#if TMPC_HX_NOSTREAM   // timing experiment only (wrong answers): no streamed band entries
-      return s;
-#endif
     }
     while (j <= jmax) {
 #pragma unroll
@@ -1075,7 +1039,7 @@ __global__ void __launch_bounds__(HARD_PCG_THREADS) k_hard_pcg(int B, int W, int
   double nu = h_block_sum_db(part, red, nsum);
   HX_SETUP(3);
   int it_done = max_iter;
-#if TMPC_HX_STAMPS   // timing experiment: per-phase shader-clock sums of every wave of problem 0
+#ifdef TMPC_HX_STAMPS   // timing experiment: per-phase shader-clock sums of every wave of problem 0
   unsigned long long hs_[8] = {}, hs_prev_ = __builtin_amdgcn_s_memtime();
 #define HX_STAMP(i_) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); hs_[i_] += n_ - hs_prev_; hs_prev_ = n_; }
 #else
@@ -1140,7 +1104,7 @@ __global__ void __launch_bounds__(HARD_PCG_THREADS) k_hard_pcg(int B, int W, int
     nu = nup;
     HX_STAMP(7);
   }
-#if TMPC_HX_STAMPS
+#ifdef TMPC_HX_STAMPS
   if (b == 0 && (t & 63) == 0 && t < D)
     printf("hx_stamps wave %d it %d D %d: top %llu spmv %llu sum_a %llu upd %llu bar %llu precond %llu sum_nu %llu pupd %llu\n",
            t >> 6, it_done, D, hs_[0], hs_[1], hs_[2], hs_[3], hs_[4], hs_[5], hs_[6], hs_[7]);
@@ -1457,8 +1421,6 @@ __global__ void __launch_bounds__(256) k_hard_ls(const ConstrDev* __restrict__ C
 }
 
 // ---------------------------------------------------------------- launchers
-#define HGRID(n, bs) dim3(((n) + (bs) - 1) / (bs)), dim3(bs)
-
 template <int NJ>
 struct LaunchHard {
   static void run(hipStream_t s, const HardArgs& h) {
@@ -1466,68 +1428,66 @@ struct LaunchHard {
     const int B = h.B, N = h.N;
     if (h.phase == 0) {
       if (!h.rows_given)   // the plugin-hook QP brings its rows (cnt / hcol / hsgn / hval) from the host
-        hipLaunchKernelGGL((k_hard_rows<NJ>), HGRID(B * N, 256), 0, s, h.Cs, B, N, h.rmax, h.x, h.u, h.active, h.cnt,
+        hipLaunchKernelGGL((k_hard_rows<NJ>), TMPC_GRID(B * N, 256), 0, s, h.Cs, B, N, h.rmax, h.x, h.u, h.active, h.cnt,
                            h.hcol, h.hsgn, h.hval, h.hslot, h.amask, h.iter, h.Wtr, h.tr_active);
       hipLaunchKernelGGL(k_hard_layout, dim3(B), dim3(64), 0, s, B, N, NX, h.rmax, h.active, h.cnt, h.roff, h.hoff,
                          h.dim, h.rkind, h.rknot, h.ridx, h.dmax);
       hipLaunchKernelGGL((k_hard_schur<NJ>), dim3(B), dim3(256), hard_schur_lds_bytes(N, NJ, h.dmax), s, h.C, B, N, h.W, h.dmax, h.rmax, h.active, h.Ghat,
                          h.per_knot, h.A, h.Bm, h.cvec, h.x, h.u, h.jsoft, h.dim, h.rkind, h.rknot, h.ridx, h.hoff,
                          h.hcol, h.hsgn, h.hval, h.Y, h.PK, h.Sb, h.gam, h.rng, h.gvec);
-    } else if (h.phase == 1) {
-      if (h.precond == 0) {
-        hipLaunchKernelGGL(k_hard_direct, dim3(B), dim3(256), 0, s, B, N, NX, h.W, h.dmax, h.rmax, h.active, h.dim,
-                           h.hoff, h.cnt, h.hcol, h.hsgn, h.Sb, h.gam, h.M, h.rhs, h.lam, h.sing,
-                           h.rng);
-      } else {
-        // the whole LDS: one 16-wave workgroup per CU, the rest of it caches preconditioner blocks
-        size_t lds = HARD_PCG_LDS_BYTES;
-        if (const char* e = getenv("TMPC_HARD_PCG_LDS_KB"))   // dev: a smaller block cache (measurement)
-          lds = std::min(lds, std::max((size_t)atoi(e) * 1024,
-                                       (size_t)hard_pcg_cache_offset(h.dmax, NX, HARD_PCG_MAX_SLOTS) * sizeof(double)));
-        const int slots = (h.dmax + HARD_PCG_THREADS - 1) / HARD_PCG_THREADS;
-#define HPCG(SL) hipLaunchKernelGGL((k_hard_pcg<NX, SL>), dim3(B), dim3(HARD_PCG_THREADS), lds, s, B, h.W, h.dmax, \
-                                    h.precond, h.active, h.dim, h.Sb, h.gam, h.tol, h.max_iter, h.Pd, h.Pl, \
-                                    h.Ptr, h.lam, h.iters, h.rng, h.work, (int)lds)
-        if (slots <= 1) HPCG(1);
-        else if (slots <= 2) HPCG(2);
-        else if (slots <= 3) HPCG(3);
-        else HPCG(4);
-#undef HPCG
-      }
+    } else if (h.phase == 1) {   // the direct solve (precond 0); the iterative one is pcg() below
+      hipLaunchKernelGGL(k_hard_direct, dim3(B), dim3(256), 0, s, B, N, NX, h.W, h.dmax, h.rmax, h.active, h.dim,
+                         h.hoff, h.cnt, h.hcol, h.hsgn, h.Sb, h.gam, h.M, h.rhs, h.lam, h.sing,
+                         h.rng);
     } else if (h.phase == 2) {
-      hipLaunchKernelGGL((k_hard_dxu<NJ>), HGRID(B * N, 64), 0, s, h.C, B, N, h.dmax, h.rmax, h.active, h.Ghat,
+      hipLaunchKernelGGL((k_hard_dxu<NJ>), TMPC_GRID(B * N, 64), 0, s, h.C, B, N, h.dmax, h.rmax, h.active, h.Ghat,
                          h.per_knot, h.A, h.Bm, h.x, h.u, h.jsoft, h.roff, h.hoff, h.cnt, h.hcol, h.hsgn, h.lam, h.dx,
                          h.du, h.gvec);
     } else {
-      hipLaunchKernelGGL((k_hard_ls<NJ>), HGRID(B * h.T * N, 256), 0, s, h.Cs, B, N, h.T, h.alphas, h.x, h.u, h.dx,
+      hipLaunchKernelGGL((k_hard_ls<NJ>), TMPC_GRID(B * h.T * N, 256), 0, s, h.Cs, B, N, h.T, h.alphas, h.x, h.u, h.dx,
                          h.du, h.active, h.hterms);
     }
   }
+  // phase 1 with a preconditioner
+  static void pcg(hipStream_t s, const HardArgs& h) {
+    constexpr int NX = 2 * NJ;
+    // the whole LDS: one 16-wave workgroup per CU, the rest of it caches preconditioner blocks
+    size_t lds = HARD_PCG_LDS_BYTES;
+    if (const char* e = getenv("TMPC_HARD_PCG_LDS_KB"))   // dev: a smaller block cache (measurement)
+      lds = std::min(lds, std::max((size_t)atoi(e) * 1024,
+                                   (size_t)hard_pcg_cache_offset(h.dmax, NX, HARD_PCG_MAX_SLOTS) * sizeof(double)));
+    const int slots = (h.dmax + HARD_PCG_THREADS - 1) / HARD_PCG_THREADS;
+#define HPCG(SL) hipLaunchKernelGGL((k_hard_pcg<NX, SL>), dim3(h.B), dim3(HARD_PCG_THREADS), lds, s, h.B, h.W, h.dmax, \
+                                    h.precond, h.active, h.dim, h.Sb, h.gam, h.tol, h.max_iter, h.Pd, h.Pl, \
+                                    h.Ptr, h.lam, h.iters, h.rng, h.work, (int)lds)
+    if (slots <= 1) HPCG(1);
+    else if (slots <= 2) HPCG(2);
+    else if (slots <= 3) HPCG(3);
+    else HPCG(4);
+#undef HPCG
+  }
 };
 
+// (two dispatches: the k_hard_pcg instances are first named after every phase kernel, as hard_set_max_lds
+// lists them, which keeps them together at the end of the code object)
 int launch_hard(hipStream_t s, int nj, const HardArgs& h) {
-  switch (nj) {
-    case 1: LaunchHard<1>::run(s, h); break;
-    case 2: LaunchHard<2>::run(s, h); break;
-    case 3: LaunchHard<3>::run(s, h); break;
-    case 4: LaunchHard<4>::run(s, h); break;
-    case 5: LaunchHard<5>::run(s, h); break;
-    case 6: LaunchHard<6>::run(s, h); break;
-    case 7: LaunchHard<7>::run(s, h); break;
-    default: return -2;
-  }
-  return 0;
+  if (h.phase != 1 || h.precond == 0)
+    return for_nj<1, NJ_FULL>(nj, [&](auto n) { LaunchHard<decltype(n)::value>::run(s, h); });
+  return for_nj<1, NJ_FULL>(nj, [&](auto n) { LaunchHard<decltype(n)::value>::pcg(s, h); });
 }
 
 int hard_set_max_lds() {
-  const int bytes = HARD_PCG_LDS_BYTES;
   int err = 0;
-#define SETH1(V, SL) err |= (int)hipFuncSetAttribute((const void*)k_hard_pcg<V, SL>, \
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-#define SETH(V) SETH1(V, 1) SETH1(V, 2) SETH1(V, 3) SETH1(V, 4)
-  SETH(2) SETH(4) SETH(6) SETH(8) SETH(10) SETH(12) SETH(14)
-#undef SETH
-#undef SETH1
+  auto set = [&](auto* kernel) {
+    err |= (int)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, HARD_PCG_LDS_BYTES);
+  };
+  for_each_nj<1, NJ_FULL>([&](auto n) {
+    constexpr int NX = 2 * decltype(n)::value;
+    set(k_hard_pcg<NX, 1>);
+    set(k_hard_pcg<NX, 2>);
+    set(k_hard_pcg<NX, 3>);
+    set(k_hard_pcg<NX, 4>);
+  });
   return err;
 }
 

@@ -300,12 +300,11 @@ __global__ void __launch_bounds__(MAXT) k_qp_blocks(int B, int N, int precond, c
 
 template <int NJ>
 struct LaunchHooks {
-  static int ghat(hipStream_t s, int B, int N, const double* G, const double* rho, double* Gh, int* err) {
+  static void ghat(hipStream_t s, int B, int N, const double* G, const double* rho, double* Gh, int* err) {
     constexpr int n = 3 * NJ;
     hipLaunchKernelGGL((k_ghat_full<n>), dim3(B * N), dim3(64), 0, s, B, N, 2 * NJ, NJ, G, rho, Gh, err);
-    return 0;
   }
-  static int qp(hipStream_t s, int B, int N, int precond, int mode, const double* Gh, const double* g,
+  static void qp(hipStream_t s, int B, int N, int precond, int mode, const double* Gh, const double* g,
                 const double* A, const double* Bm, const double* c, const int* err, double tol, int max_iter,
                 const double* guess, int* iters, double* dx, double* du, double* lam, double* Sd, double* Sl,
                 double* gam) {
@@ -329,7 +328,6 @@ struct LaunchHooks {
     }
 #undef TMPC_QPB_LAUNCH
 #undef TMPC_QPB_ARGS
-    return 0;
   }
   static int set_lds(int bytes) {
     int e = 0;
@@ -343,26 +341,8 @@ struct LaunchHooks {
   }
 };
 
-#ifdef TMPC_DEV_NJ
-#define TMPC_HOOKS_NJ(nj, CALL)                 \
-  if (nj != TMPC_DEV_NJ) return -2;              \
-  return LaunchHooks<TMPC_DEV_NJ>::CALL;
-#else
-#define TMPC_HOOKS_NJ(nj, CALL)                  \
-  switch (nj) {                                  \
-    case 1: return LaunchHooks<1>::CALL;         \
-    case 2: return LaunchHooks<2>::CALL;         \
-    case 3: return LaunchHooks<3>::CALL;         \
-    case 4: return LaunchHooks<4>::CALL;         \
-    case 5: return LaunchHooks<5>::CALL;         \
-    case 6: return LaunchHooks<6>::CALL;         \
-    case 7: return LaunchHooks<7>::CALL;         \
-    default: return -2;                          \
-  }
-#endif
-
 int launch_ghat_full(hipStream_t s, int nj, int B, int N, const double* G, const double* rho, double* Gh, int* err) {
-  TMPC_HOOKS_NJ(nj, ghat(s, B, N, G, rho, Gh, err))
+  return for_nj<1, NJ_FULL>(nj, [&](auto n) { LaunchHooks<decltype(n)::value>::ghat(s, B, N, G, rho, Gh, err); });
 }
 
 int launch_qp_blocks(hipStream_t s, int nj, int B, int N, int precond, int mode, const double* Gh, const double* g,
@@ -372,19 +352,16 @@ int launch_qp_blocks(hipStream_t s, int nj, int B, int N, int precond, int mode,
   const int rows = N * 2 * nj;
   if (rows > 1024) return -1;
   if (qpb_lds_doubles(N, 2 * nj, nj) * sizeof(double) > 160 * 1024) return -3;
-  TMPC_HOOKS_NJ(nj, qp(s, B, N, precond, mode, Gh, g, A, Bm, c, err, tol, max_iter, guess, iters, dx, du, lam, Sd,
-                       Sl, gam))
+  return for_nj<1, NJ_FULL>(nj, [&](auto n) {
+    LaunchHooks<decltype(n)::value>::qp(s, B, N, precond, mode, Gh, g, A, Bm, c, err, tol, max_iter, guess, iters, dx,
+                                        du, lam, Sd, Sl, gam);
+  });
 }
 
 int qp_blocks_set_max_lds() {
-  const int bytes = 160 * 1024;
-#ifdef TMPC_DEV_NJ
-  return LaunchHooks<TMPC_DEV_NJ>::set_lds(bytes);
-#else
-  return LaunchHooks<1>::set_lds(bytes) | LaunchHooks<2>::set_lds(bytes) | LaunchHooks<3>::set_lds(bytes) |
-         LaunchHooks<4>::set_lds(bytes) | LaunchHooks<5>::set_lds(bytes) | LaunchHooks<6>::set_lds(bytes) |
-         LaunchHooks<7>::set_lds(bytes);
-#endif
+  int e = 0;
+  for_each_nj<1, NJ_FULL>([&](auto n) { e |= LaunchHooks<decltype(n)::value>::set_lds(160 * 1024); });
+  return e;
 }
 
 }  // namespace tmpc

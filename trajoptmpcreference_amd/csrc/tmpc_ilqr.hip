@@ -644,24 +644,12 @@ struct FwdPf {
   static __host__ __device__ size_t lds_doubles(int T) { return 2 * (rk(T) + rs(T)); }
 };
 
-// The knot loop's memory waits (config 3, profiles/r05/configs/c3_fwd_*_r05a[e-g]*; each switch 0 restores
-// the round-4 form for comparison): the next knot's prefetch issued after this knot's stores and feedback
-// reads (PF_LATE: in front of them, the compiler's wait pass put a vmcnt(0) before the feedback's LDS
-// reads -- the LDS-DMA may alias them -- exposing the DMA's latency), explicit waits after the loads into
-// xh / uh (WAITS), the DMA sources precomputed (PFR), the knot's wait through the builtin (BWAIT):
+// The knot loop's memory waits (config 3, profiles/r05/configs/c3_fwd_*_r05a[e-g]*; DESIGN.md 4i has the
+// round-4 forms they replaced): the next knot's prefetch issued after this knot's stores and feedback
+// reads (in front of them, the compiler's wait pass put a vmcnt(0) before the feedback's LDS reads -- the
+// LDS-DMA may alias them -- exposing the DMA's latency), explicit waits after the loads into xh / uh, the
+// DMA sources precomputed, the knot's wait through the builtin:
 // ilqr_forward 0.472 -> 0.401 ms per launch, config 3 4.37k -> 4.65k solves/s
-#ifndef TMPC_FWD_PF_LATE
-#define TMPC_FWD_PF_LATE 1
-#endif
-#ifndef TMPC_FWD_WAITS
-#define TMPC_FWD_WAITS 1
-#endif
-#ifndef TMPC_FWD_PFR
-#define TMPC_FWD_PFR 1
-#endif
-#ifndef TMPC_FWD_BWAIT
-#define TMPC_FWD_BWAIT 1
-#endif
 template <int NJ, bool CHAIN, bool SOFT, class MT, class R, bool PF>
 __global__ void __launch_bounds__(64) k_ilqr_forward(MT Mg, const CostDev* __restrict__ C,
                                                      const ConstrDev* __restrict__ Cs, const double* __restrict__ mu,
@@ -714,14 +702,14 @@ __global__ void __launch_bounds__(64) k_ilqr_forward(MT Mg, const CostDev* __res
     if (lane < npt) s_pb[lane] = P.at(min(p0 + lane, np - 1));
     __syncthreads();
   }
-  // TMPC_FWD_PFR: each lane's LDS-DMA sources for knot 0 computed once, here, while no LDS-DMA is in
+  // Each lane's LDS-DMA sources for knot 0 computed once, here, while no LDS-DMA is in
   // flight (up to PFJ wave-instructions per kind: T >= 5 trials); knot kn's are base + kn x stride.
   // Reading the problem slot from LDS per instruction inside the prefetch made the compiler wait for
   // the previous LDS-DMA before every read (the DMA writes LDS): ~3.7k cycles per knot to issue 13
   // instructions (profiles/r05/configs/c3_fwd_stamps_r05ae.txt)
   constexpr int PFJ = 12;
   const int nkj = (npf * PF_::CK + 63) / 64, nsj = (npf * 2 * PF_::SS + 63) / 64;
-  const bool pfr = TMPC_FWD_PFR && pf && nkj <= PFJ && nsj <= PFJ;
+  const bool pfr = pf && nkj <= PFJ && nsj <= PFJ;
   const double* kbase[PFJ];
   const char* sbase[PFJ];
   int sstride[PFJ];   // bytes per knot
@@ -789,7 +777,7 @@ __global__ void __launch_bounds__(64) k_ilqr_forward(MT Mg, const CostDev* __res
   // that could still be in flight into xh / uh when the loop's paths join made the pass put a full
   // vmcnt(0) inside the knot loop, which also waited for the next knot's prefetch (its latency on
   // every knot's critical path instead of under the dynamics)
-  if (TMPC_FWD_WAITS) __builtin_amdgcn_s_waitcnt(0x0F70);
+  __builtin_amdgcn_s_waitcnt(0x0F70);
   double J = 0.0;
 #ifdef TMPC_ILQR_STAMPS
   unsigned long long st_[8] = {}, st_prev_ = __builtin_amdgcn_s_memtime();
@@ -799,13 +787,11 @@ __global__ void __launch_bounds__(64) k_ilqr_forward(MT Mg, const CostDev* __res
     const bool term = k == K;
     double uh[NU];
     if (pf && !term) {
-      // knot k's operands have landed in LDS.  TMPC_FWD_BWAIT: through the builtin, which is no
-      // compiler memory barrier (the asm's "memory" clobber made every knot reload the cost's
+      // knot k's operands have landed in LDS.  The wait goes through the builtin, which is no
+      // compiler memory barrier (an asm's "memory" clobber made every knot reload the cost's
       // constants); the compiler's own wait pass orders LDS reads after the LDS-DMA writing them
-      if (TMPC_FWD_BWAIT) __builtin_amdgcn_s_waitcnt(0x0F70);
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_waitcnt(0x0F70);
       IL_STAMP(4);
-      if (!TMPC_FWD_PF_LATE && k + 1 < K) prefetch(k + 1, (k + 1) & 1);
       IL_STAMP(5);
     }
     if (live) {
@@ -816,13 +802,13 @@ __global__ void __launch_bounds__(64) k_ilqr_forward(MT Mg, const CostDev* __res
     } else {
 #pragma unroll
       for (int m = 0; m < NX; ++m) xh[m] = xb[m * N + k];
-      if (TMPC_FWD_WAITS) __builtin_amdgcn_s_waitcnt(0x0F70);
+      __builtin_amdgcn_s_waitcnt(0x0F70);
     }
     if (!term) {
       if (init) {
 #pragma unroll
         for (int i = 0; i < NU; ++i) uh[i] = ub[i * K + k];
-        if (TMPC_FWD_WAITS) __builtin_amdgcn_s_waitcnt(0x0F70);
+        __builtin_amdgcn_s_waitcnt(0x0F70);
       } else if (pf) {
         const double* buf = pfb + (size_t)(k & 1) * (PF_::rk(T) + PF_::rs(T));
         const double* Kk = buf + (size_t)pl * PF_::SK;
@@ -867,8 +853,8 @@ __global__ void __launch_bounds__(64) k_ilqr_forward(MT Mg, const CostDev* __res
       }
     }
     }   // live
-    // TMPC_FWD_PF_LATE: the next knot's prefetch after this knot's stores
-    if (TMPC_FWD_PF_LATE && pf && k + 1 < K) prefetch(k + 1, (k + 1) & 1);
+    // the next knot's prefetch after this knot's stores
+    if (pf && k + 1 < K) prefetch(k + 1, (k + 1) & 1);
     if (live) {
     IL_STAMP(0);
     J = J + knot_quad_cost<NJ>(C, k, N, xh, uh, term);
@@ -1140,10 +1126,10 @@ __global__ void __launch_bounds__(64) k_ilqr_decide(PList P, int B, int N, int N
 }
 
 // ======================================================================= launchers
-#define TMPC_GRID(n, bs) dim3(((n) + (bs) - 1) / (bs)), dim3(bs)
 
-template <int NJ, bool CHAIN, class MT>
-struct LaunchIlqr {
+// the backward sweep and the initial cost depend on the joint count only
+template <int NJ>
+struct LaunchIlqrNJ {
   static void backward(bool f32, hipStream_t s, const CostDev* C, const ConstrDev* Cs, PList P, int B, int N, const double* x,
                        const double* u, const double* rho, const int* active, const double* A, const double* Bm,
                        const double* mu, const double* lam, double* jscratch, double* K, double* d, double* dV,
@@ -1179,6 +1165,21 @@ struct LaunchIlqr {
                            Bm, mu, lam, js, K, d, dV, ok);
     }
   }
+  static void init_cost(hipStream_t s, const CostDev* C, const ConstrDev* Cs, const double* mu, const double* lam, PList P,
+                        int B, int N, const double* x, const double* u, const int* mask, double* Jt) {
+    const size_t lds = (size_t)2 * N * sizeof(double);
+    if constexpr (!kWide<NJ>) {   // a wide model: no soft limits (launch_ilqr_init_cost refuses them)
+      if (mu) {
+        hipLaunchKernelGGL((k_ilqr_init_cost<NJ, true>), dim3(B), dim3(64), lds, s, C, Cs, mu, lam, P, B, N, x, u, mask, Jt);
+        return;
+      }
+    }
+    hipLaunchKernelGGL((k_ilqr_init_cost<NJ, false>), dim3(B), dim3(64), lds, s, C, Cs, mu, lam, P, B, N, x, u, mask, Jt);
+  }
+};
+
+template <int NJ, bool CHAIN, class MT>
+struct LaunchIlqr {
   static void forward(bool f32, hipStream_t s, const ModelDev* M, const CostDev* C, const ConstrDev* Cs, const double* mu,
                       const double* lam, PList P, int B, int N, int T, double dt, int init, const double* alphas,
                       const double* x, const double* u, const double* K, const double* d, const int* active,
@@ -1213,69 +1214,37 @@ struct LaunchIlqr {
   }
 };
 
-// (Unlike tmpc_fd.hip / tmpc_kernels.hip, a runtime chain model keeps the CHAIN instance here: the rollout
-// measured 2.1 ms per launch on it against 3.2 ms on the general-topology one, arm6 B = 4096.)
-#define TMPC_DISPATCH_ILQR(nj, chain, CALL)                                                              \
-  switch (mid) {                                                                                       \
-    TMPC_STATIC_MODEL_CASES(LaunchIlqr, CALL)                                                            \
-    default: break;                                                                                    \
-  }                                                                                                    \
-  switch (nj) {                                                                                        \
-    case 1: if (chain) LaunchIlqr<1, true, ModelRef>::CALL; else LaunchIlqr<1, false, ModelRef>::CALL; break;  \
-    case 2: if (chain) LaunchIlqr<2, true, ModelRef>::CALL; else LaunchIlqr<2, false, ModelRef>::CALL; break;  \
-    case 3: if (chain) LaunchIlqr<3, true, ModelRef>::CALL; else LaunchIlqr<3, false, ModelRef>::CALL; break;  \
-    case 4: if (chain) LaunchIlqr<4, true, ModelRef>::CALL; else LaunchIlqr<4, false, ModelRef>::CALL; break;  \
-    case 5: if (chain) LaunchIlqr<5, true, ModelRef>::CALL; else LaunchIlqr<5, false, ModelRef>::CALL; break;  \
-    case 6: if (chain) LaunchIlqr<6, true, ModelRef>::CALL; else LaunchIlqr<6, false, ModelRef>::CALL; break;  \
-    case 7: if (chain) LaunchIlqr<7, true, ModelRef>::CALL; else LaunchIlqr<7, false, ModelRef>::CALL; break;  \
-    TMPC_WIDE_CASES(LaunchIlqr, CALL)                                                                  \
-    default: return -2;                                                                                \
-  }                                                                                                    \
-  return 0;
-
 int launch_ilqr_backward(bool f32, hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, PList P, int B, int N,
                          const double* x, const double* u, const double* rho, const int* active, const double* A,
                          const double* Bm, const double* mu, const double* lam, double* jscratch, double* K,
                          double* d, double* dV, int* ok) {
-  const int mid = 0;
-  TMPC_DISPATCH_ILQR(nj, true, backward(f32, s, C, Cs, P, B, N, x, u, rho, active, A, Bm, mu, lam, jscratch, K, d, dV,
-                                        ok))
+  return for_nj<1, NJMAX>(nj, [&](auto n) {
+    LaunchIlqrNJ<decltype(n)::value>::backward(f32, s, C, Cs, P, B, N, x, u, rho, active, A, Bm, mu, lam, jscratch, K, d,
+                                               dV, ok);
+  });
 }
 
+// (Unlike tmpc_fd.hip / tmpc_kernels.hip, a runtime chain model keeps the CHAIN instance here: the rollout
+// measured 2.1 ms per launch on it against 3.2 ms on the general-topology one, arm6 B = 4096.)
 int launch_ilqr_forward(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, const CostDev* C,
                         const ConstrDev* Cs, const double* mu, const double* lam, PList P, int B, int N, int T,
                         double dt, int init, const double* alphas, const double* x, const double* u, const double* K,
                         const double* d, const int* active, const int* ok, double* xt, double* ut, double* Jt) {
-  TMPC_DISPATCH_ILQR(nj, chain, forward(f32, s, M, C, Cs, mu, lam, P, B, N, T, dt, init, alphas, x, u, K, d, active, ok,
-                                        xt, ut, Jt))
+  return dispatch_model(mid, nj, chain, [&](auto t) {
+    using Tag = decltype(t);
+    LaunchIlqr<Tag::nj, Tag::chain, typename Tag::model>::forward(f32, s, M, C, Cs, mu, lam, P, B, N, T, dt, init, alphas,
+                                                                  x, u, K, d, active, ok, xt, ut, Jt);
+  });
 }
 
 int launch_ilqr_init_cost(hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, const double* mu,
                           const double* lam, PList P, int B, int N, const double* x, const double* u, const int* mask,
                           double* Jt) {
-  const size_t lds = (size_t)2 * N * sizeof(double);
-  if (lds > 64 * 1024) return -1;
-#define TMPC_INIT_COST(V)                                                                                      \
-  case V:                                                                                                      \
-    if (mu)                                                                                                    \
-      hipLaunchKernelGGL((k_ilqr_init_cost<V, true>), dim3(B), dim3(64), lds, s, C, Cs, mu, lam, P, B, N, x, u, mask, Jt); \
-    else                                                                                                       \
-      hipLaunchKernelGGL((k_ilqr_init_cost<V, false>), dim3(B), dim3(64), lds, s, C, Cs, mu, lam, P, B, N, x, u, mask, Jt); \
-    return 0;
-  switch (nj) {
-    TMPC_INIT_COST(1) TMPC_INIT_COST(2) TMPC_INIT_COST(3) TMPC_INIT_COST(4) TMPC_INIT_COST(5) TMPC_INIT_COST(6)
-    TMPC_INIT_COST(7)
-#define TMPC_INIT_COST_WIDE(V)   /* a wide model: no soft limits */                                         \
-  case V:                                                                                                      \
-    if (mu) return -2;                                                                                         \
-    hipLaunchKernelGGL((k_ilqr_init_cost<V, false>), dim3(B), dim3(64), lds, s, C, Cs, mu, lam, P, B, N, x, u, mask, Jt); \
-    return 0;
-    TMPC_INIT_COST_WIDE(8) TMPC_INIT_COST_WIDE(9) TMPC_INIT_COST_WIDE(10) TMPC_INIT_COST_WIDE(11)
-    TMPC_INIT_COST_WIDE(12)
-#undef TMPC_INIT_COST_WIDE
-    default: return -2;
-  }
-#undef TMPC_INIT_COST
+  if ((size_t)2 * N * sizeof(double) > 64 * 1024) return -1;
+  if (nj > NJ_FULL && mu) return -2;   // a wide model: no soft limits
+  return for_nj<1, NJMAX>(nj, [&](auto n) {
+    LaunchIlqrNJ<decltype(n)::value>::init_cost(s, C, Cs, mu, lam, P, B, N, x, u, mask, Jt);
+  });
 }
 
 void launch_ilqr_decide(hipStream_t s, PList P, int B, int N, int NX, int NU, int T, int init, const double* alphas,

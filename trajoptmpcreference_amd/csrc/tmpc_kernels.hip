@@ -1164,22 +1164,15 @@ __global__ void __launch_bounds__(256) k_unit_grad(MT M, int K, double dt,
 }
 
 // ======================================================================= launchers
-#define TMPC_GRID(n, bs) dim3(((n) + (bs) - 1) / (bs)), dim3(bs)
-
 // f32: the dynamics in fp32 (tmpc_options.precision F32 / MIXED), fp64 in and out
 template <int NJ, bool CHAIN, class MT>
 struct Launch {
   static void qp_minv(bool f32, hipStream_t s, const ModelDev* M, PList P, int B, int N, const double* x,
                       const int* need, double* minv) {
-    if constexpr (!kWide<NJ>) {   // fp32 instances for up to NJ_FULL joints only
-      if (f32) {
-        hipLaunchKernelGGL((k_qp_minv<NJ, CHAIN, MT, float>), TMPC_GRID(B * (N - 1) * NJ, 256), 0, s, MT::make(M), P, B, N,
-                           x, need, minv);
-        return;
-      }
-    }
-    hipLaunchKernelGGL((k_qp_minv<NJ, CHAIN, MT, double>), TMPC_GRID(B * (N - 1) * NJ, 256), 0, s, MT::make(M), P, B, N,
-                       x, need, minv);
+    with_real<NJ>(f32, [&](auto r) {
+      hipLaunchKernelGGL((k_qp_minv<NJ, CHAIN, MT, decltype(r)>), TMPC_GRID(B * (N - 1) * NJ, 256), 0, s, MT::make(M), P,
+                         B, N, x, need, minv);
+    });
   }
   // a runtime model (ModelRef) takes the general-topology gradient instance even for a chain: with runtime
   // coefficients the chain specialisation's unrolled recursion spills 2.5x more (k_qp_grad<6, chain,
@@ -1187,36 +1180,22 @@ struct Launch {
   static constexpr bool GCHAIN = MT::STATIC ? CHAIN : false;
   static void qp_grad(bool f32, hipStream_t s, const ModelDev* M, PList P, int B, int N, double dt, const double* x,
                       const int* need, const double* qdd, const double* minv, double* A, double* Bm) {
-    if constexpr (!kWide<NJ>) {   // fp32 instances for up to NJ_FULL joints only
-      if (f32) {
-        hipLaunchKernelGGL((k_qp_grad<NJ, GCHAIN, MT, float>), TMPC_GRID(B * (N - 1) * 2 * NJ, 256), 0, s, MT::make(M), P, B,
-                           N, dt, x, need, qdd, minv, A, Bm);
-        return;
-      }
-    }
-    hipLaunchKernelGGL((k_qp_grad<NJ, GCHAIN, MT, double>), TMPC_GRID(B * (N - 1) * 2 * NJ, 256), 0, s, MT::make(M), P,
-                       B, N, dt, x, need, qdd, minv, A, Bm);
+    with_real<NJ>(f32, [&](auto r) {
+      hipLaunchKernelGGL((k_qp_grad<NJ, GCHAIN, MT, decltype(r)>), TMPC_GRID(B * (N - 1) * 2 * NJ, 256), 0, s,
+                         MT::make(M), P, B, N, dt, x, need, qdd, minv, A, Bm);
+    });
   }
   static void unit_minv(bool f32, hipStream_t s, const ModelDev* M, int K, const double* x, double* minv) {
-    if constexpr (!kWide<NJ>) {   // fp32 instances for up to NJ_FULL joints only
-      if (f32) {
-        hipLaunchKernelGGL((k_unit_minv<NJ, CHAIN, MT, float>), TMPC_GRID(K * NJ, 256), 0, s, MT::make(M), K, x, minv);
-        return;
-      }
-    }
-    hipLaunchKernelGGL((k_unit_minv<NJ, CHAIN, MT, double>), TMPC_GRID(K * NJ, 256), 0, s, MT::make(M), K, x, minv);
+    with_real<NJ>(f32, [&](auto r) {
+      hipLaunchKernelGGL((k_unit_minv<NJ, CHAIN, MT, decltype(r)>), TMPC_GRID(K * NJ, 256), 0, s, MT::make(M), K, x, minv);
+    });
   }
   static void unit_grad(bool f32, hipStream_t s, const ModelDev* M, int K, double dt, const double* x, const double* qdd,
                         const double* minv, double* A, double* Bm, double* dqdd) {
-    if constexpr (!kWide<NJ>) {   // fp32 instances for up to NJ_FULL joints only
-      if (f32) {
-        hipLaunchKernelGGL((k_unit_grad<NJ, GCHAIN, MT, float>), TMPC_GRID(K * 2 * NJ, 256), 0, s, MT::make(M), K, dt, x, qdd,
-                           minv, A, Bm, dqdd);
-        return;
-      }
-    }
-    hipLaunchKernelGGL((k_unit_grad<NJ, GCHAIN, MT, double>), TMPC_GRID(K * 2 * NJ, 256), 0, s, MT::make(M), K, dt, x, qdd,
-                       minv, A, Bm, dqdd);
+    with_real<NJ>(f32, [&](auto r) {
+      hipLaunchKernelGGL((k_unit_grad<NJ, GCHAIN, MT, decltype(r)>), TMPC_GRID(K * 2 * NJ, 256), 0, s, MT::make(M), K, dt,
+                         x, qdd, minv, A, Bm, dqdd);
+    });
   }
 };
 
@@ -1276,53 +1255,40 @@ struct LaunchNJ {
   static void ginv_soft(hipStream_t s, const CostDev* C, const ConstrDev* Cs, PList P, int B, int N, const double* rho,
                         const int* active, const double* x, const double* u, const double* mu, const double* lam,
                         double* Gk, double* jsoft) {
-    if constexpr (!kWide<NJ>) {   // no soft limits on a wide model (launch_ginv_soft refuses it)
-      const int wpp = (2 * N + 4 * GINV_SOFT_GROUPS - 1) / (4 * GINV_SOFT_GROUPS);
-      hipLaunchKernelGGL((k_ginv_soft<NJ>), dim3(B * wpp), dim3(64), 0, s, C, Cs, P, B, N, rho, active, x, u, mu, lam,
-                         Gk, jsoft);
-    }
+    const int wpp = (2 * N + 4 * GINV_SOFT_GROUPS - 1) / (4 * GINV_SOFT_GROUPS);
+    hipLaunchKernelGGL((k_ginv_soft<NJ>), dim3(B * wpp), dim3(64), 0, s, C, Cs, P, B, N, rho, active, x, u, mu, lam, Gk,
+                       jsoft);
   }
 };
 
+// the Schur dimensions of the stand-alone PCG (tmpc_pcg_batch): nx = 2, 4, ... 16
+constexpr int PCG_NX_MAX = 16;
+
+// set(kernel) for every k_qp instance of NJ joints with (PK) or without the per-knot Ghat of the soft limits
+template <int NJ, bool PK, int MD = QP_MODE_PCG, class F>
+void for_each_qp(F&& set) {
+  if constexpr (MD <= QP_MODE_DXU) {
+    set(k_qp<NJ, 1, 768, PK, MD>);
+    set(k_qp<NJ, 2, 512, PK, MD>);
+    if constexpr (!kWide<NJ>) set(k_qp<NJ, 2, QP_MAX_ROWS / 2, PK, MD, true>);   // S / P^-1 rows in HBM
+    for_each_qp<NJ, PK, MD + 1>(set);
+  }
+}
+
 int pcg_set_max_lds() {
-  const int bytes = 160 * 1024;
   int err = 0;
-#define SETA(V)                                                                                                    \
-  err |= (int)hipFuncSetAttribute((const void*)k_pcg<V, 1, 768>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); \
-  err |= (int)hipFuncSetAttribute((const void*)k_pcg<V, 2, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-#ifdef TMPC_DEV_NJ
-  SETA(2 * TMPC_DEV_NJ)
-#else
-  SETA(2) SETA(4) SETA(6) SETA(8) SETA(10) SETA(12) SETA(14) SETA(16)
-#endif
-#undef SETA
-#define SETQ2(V, P, MD)                                                                                  \
-  err |= (int)hipFuncSetAttribute((const void*)k_qp<V, 1, 768, P, MD>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  bytes);                                                              \
-  err |= (int)hipFuncSetAttribute((const void*)k_qp<V, 2, 512, P, MD>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  bytes);                                                              \
-  err |= (int)hipFuncSetAttribute((const void*)k_qp<V, 2, QP_MAX_ROWS / 2, P, MD, true>,                          \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-#define SETQ1(V, P) SETQ2(V, P, QP_MODE_PCG) SETQ2(V, P, QP_MODE_SCHUR) SETQ2(V, P, QP_MODE_DXU)
-#define SETQ(V) SETQ1(V, false) SETQ1(V, true)
-#ifdef TMPC_DEV_NJ
-  SETQ(TMPC_DEV_NJ)
-#else
-  SETQ(1) SETQ(2) SETQ(3) SETQ(4) SETQ(5) SETQ(6) SETQ(7)
-  // the wide models' instances (registers / two rows per lane, no soft limits)
-#define SETQW1(V, MD)                                                                                    \
-  err |= (int)hipFuncSetAttribute((const void*)k_qp<V, 1, 768, false, MD>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  bytes);                                                              \
-  err |= (int)hipFuncSetAttribute((const void*)k_qp<V, 2, 512, false, MD>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  bytes);
-#define SETQW(V) SETQW1(V, QP_MODE_PCG) SETQW1(V, QP_MODE_SCHUR) SETQW1(V, QP_MODE_DXU)
-  SETQW(8) SETQW(9) SETQW(10) SETQW(11) SETQW(12)
-#undef SETQW
-#undef SETQW1
-#endif
-#undef SETQ
-#undef SETQ1
-#undef SETQ2
+  auto set = [&](auto* kernel) {
+    err |= (int)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  };
+  for_each_nj<2, PCG_NX_MAX, 2>([&](auto nx) {
+    set(k_pcg<decltype(nx)::value, 1, 768>);
+    set(k_pcg<decltype(nx)::value, 2, 512>);
+  });
+  for_each_nj<1, NJMAX>([&](auto nj) {
+    constexpr int NJ = decltype(nj)::value;
+    for_each_qp<NJ, false>(set);
+    if constexpr (!kWide<NJ>) for_each_qp<NJ, true>(set);   // a wide model: no soft limits
+  });
   return err;
 }
 
@@ -1346,17 +1312,9 @@ int launch_pcg(hipStream_t s, int nx, int B, int N, int precond, const double* S
                const double* Su, const double* gam, const double* guess, double tol, int max_iter, double* lam,
                int* iters, double* tnu, double* tres, double* Pd) {
   if (N * nx > 1024) return -1;
-  switch (nx) {
-#define CASE_NX(V) \
-  case V: launch_pcg_nx<V>(s, B, N, precond, Sd, Sl, Su, gam, guess, tol, max_iter, lam, iters, tnu, tres, Pd); return 0;
-#ifdef TMPC_DEV_NJ
-    CASE_NX(2 * TMPC_DEV_NJ)
-#else
-    CASE_NX(2) CASE_NX(4) CASE_NX(6) CASE_NX(8) CASE_NX(10) CASE_NX(12) CASE_NX(14) CASE_NX(16)
-#endif
-#undef CASE_NX
-    default: return -2;
-  }
+  return for_nj<2, PCG_NX_MAX, 2>(nx, [&](auto v) {
+    launch_pcg_nx<decltype(v)::value>(s, B, N, precond, Sd, Sl, Su, gam, guess, tol, max_iter, lam, iters, tnu, tres, Pd);
+  });
 }
 
 void launch_ls_decide(hipStream_t s, PList P, int B, int N, int NX, int NU, int T, int mode, int soft,
@@ -1742,79 +1700,38 @@ void launch_stream_init(hipStream_t s, int B, const StreamDev& sd, double* x, do
 }
 
 
-// dispatch tables over the joint count and the chain specialisation
-#ifdef TMPC_DEV_NJ
-#define TMPC_DISPATCH_NJ(nj, chain, CALL)                                          \
-  if (nj != TMPC_DEV_NJ) return -2;                                                 \
-  if (chain) Launch<TMPC_DEV_NJ, true, ModelRef>::CALL;                             \
-  else Launch<TMPC_DEV_NJ, false, ModelRef>::CALL;                                  \
-  return 0;
-#else
-#define TMPC_DISPATCH_NJ(nj, chain, CALL)                                                              \
-  switch (mid) {                                                                                       \
-    TMPC_STATIC_MODEL_CASES(Launch, CALL)                                                            \
-    default: break;                                                                                    \
-  }                                                                                                    \
-  switch (nj) {                                                                                        \
-    case 1: if (chain) Launch<1, true, ModelRef>::CALL; else Launch<1, false, ModelRef>::CALL; break;  \
-    case 2: if (chain) Launch<2, true, ModelRef>::CALL; else Launch<2, false, ModelRef>::CALL; break;  \
-    case 3: if (chain) Launch<3, true, ModelRef>::CALL; else Launch<3, false, ModelRef>::CALL; break;  \
-    case 4: if (chain) Launch<4, true, ModelRef>::CALL; else Launch<4, false, ModelRef>::CALL; break;  \
-    case 5: if (chain) Launch<5, true, ModelRef>::CALL; else Launch<5, false, ModelRef>::CALL; break;  \
-    case 6: if (chain) Launch<6, true, ModelRef>::CALL; else Launch<6, false, ModelRef>::CALL; break;  \
-    case 7: if (chain) Launch<7, true, ModelRef>::CALL; else Launch<7, false, ModelRef>::CALL; break;  \
-    TMPC_WIDE_CASES(Launch, CALL)                                                                      \
-    default: return -2;                                                                                \
-  }                                                                                                    \
-  return 0;
-#endif
-
-#ifdef TMPC_DEV_NJ
-// experiment builds (make dev): one joint count only, a fraction of the compile time
-#define TMPC_DISPATCH_NJ2(nj, CALL)                      \
-  if (nj != TMPC_DEV_NJ) return -2;                      \
-  LaunchNJ<TMPC_DEV_NJ>::CALL;                           \
-  return 0;
-#else
-#define TMPC_DISPATCH_NJ2(nj, CALL)          \
-  switch (nj) {                              \
-    case 1: LaunchNJ<1>::CALL; break;        \
-    case 2: LaunchNJ<2>::CALL; break;        \
-    case 3: LaunchNJ<3>::CALL; break;        \
-    case 4: LaunchNJ<4>::CALL; break;        \
-    case 5: LaunchNJ<5>::CALL; break;        \
-    case 6: LaunchNJ<6>::CALL; break;        \
-    case 7: LaunchNJ<7>::CALL; break;        \
-    case 8: LaunchNJ<8>::CALL; break;        \
-    case 9: LaunchNJ<9>::CALL; break;        \
-    case 10: LaunchNJ<10>::CALL; break;      \
-    case 11: LaunchNJ<11>::CALL; break;      \
-    case 12: LaunchNJ<12>::CALL; break;      \
-    default: return -2;                      \
-  }                                                                                \
-  return 0;
-#endif
-
 int launch_qp_minv(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, PList P, int B, int N,
                    const double* x, const int* need, double* minv) {
-  TMPC_DISPATCH_NJ(nj, chain, qp_minv(f32, s, M, P, B, N, x, need, minv))
+  return dispatch_model(mid, nj, chain, [&](auto t) {
+    using T = decltype(t);
+    Launch<T::nj, T::chain, typename T::model>::qp_minv(f32, s, M, P, B, N, x, need, minv);
+  });
 }
 int launch_qp_grad(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, PList P, int B, int N,
                    double dt, const double* x, const int* need, const double* qdd, const double* minv, double* A,
                    double* Bm) {
-  TMPC_DISPATCH_NJ(nj, chain, qp_grad(f32, s, M, P, B, N, dt, x, need, qdd, minv, A, Bm))
+  return dispatch_model(mid, nj, chain, [&](auto t) {
+    using T = decltype(t);
+    Launch<T::nj, T::chain, typename T::model>::qp_grad(f32, s, M, P, B, N, dt, x, need, qdd, minv, A, Bm);
+  });
 }
 int launch_unit_minv(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, int K, const double* x,
                      double* minv) {
-  TMPC_DISPATCH_NJ(nj, chain, unit_minv(f32, s, M, K, x, minv))
+  return dispatch_model(mid, nj, chain, [&](auto t) {
+    using T = decltype(t);
+    Launch<T::nj, T::chain, typename T::model>::unit_minv(f32, s, M, K, x, minv);
+  });
 }
 int launch_unit_grad(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, int K, double dt,
                      const double* x, const double* qdd, const double* minv, double* A, double* Bm, double* dqdd) {
-  TMPC_DISPATCH_NJ(nj, chain, unit_grad(f32, s, M, K, dt, x, qdd, minv, A, Bm, dqdd))
+  return dispatch_model(mid, nj, chain, [&](auto t) {
+    using T = decltype(t);
+    Launch<T::nj, T::chain, typename T::model>::unit_grad(f32, s, M, K, dt, x, qdd, minv, A, Bm, dqdd);
+  });
 }
 int launch_ginv(hipStream_t s, int nj, const CostDev* C, PList P, int B, const double* rho, const int* active,
                 double* G) {
-  TMPC_DISPATCH_NJ2(nj, ginv(s, C, P, B, rho, active, G))
+  return for_nj<1, NJMAX>(nj, [&](auto n) { LaunchNJ<decltype(n)::value>::ginv(s, C, P, B, rho, active, G); });
 }
 int launch_qp(hipStream_t s, int nj, const CostDev* C, PList P, int B, int N, double dt, int precond, int mode,
               const double* x, const double* u,
@@ -1827,14 +1744,17 @@ int launch_qp(hipStream_t s, int nj, const CostDev* C, PList P, int B, int N, do
   const bool gm = nj <= NJ_FULL && (rows > 1024 || (rows >= qp_gm_min_rows() && mode == QP_MODE_PCG));
   if (gm && mode == QP_MODE_PCG && !Sg) return -4;
   if (qp_lds_doubles(N, 2 * nj, nj, gm ? QP_MAX_ROWS : 1024) * sizeof(double) > 160 * 1024) return -3;
-  TMPC_DISPATCH_NJ2(nj, qp(s, C, P, B, N, dt, precond, mode, x, u, active, G, A, Bm, cvec, tol, max_iter, iters, dx, du, lam,
-                           Sd, Sl, gam, Pd, jsoft, guess, Sg))
+  return for_nj<1, NJMAX>(nj, [&](auto n) {
+    LaunchNJ<decltype(n)::value>::qp(s, C, P, B, N, dt, precond, mode, x, u, active, G, A, Bm, cvec, tol, max_iter, iters,
+                                     dx, du, lam, Sd, Sl, gam, Pd, jsoft, guess, Sg);
+  });
 }
 int launch_ginv_soft(hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, PList P, int B, int N,
                      const double* rho, const int* active, const double* x, const double* u, const double* mu,
                      const double* lam, double* Gk, double* jsoft) {
-  if (nj > NJ_FULL) return -2;
-  TMPC_DISPATCH_NJ2(nj, ginv_soft(s, C, Cs, P, B, N, rho, active, x, u, mu, lam, Gk, jsoft))
+  return for_nj<1, NJ_FULL>(nj, [&](auto n) {   // no soft limits on a wide model
+    LaunchNJ<decltype(n)::value>::ginv_soft(s, C, Cs, P, B, N, rho, active, x, u, mu, lam, Gk, jsoft);
+  });
 }
 
 }  // namespace tmpc
