@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-#define TMPC_ABI_VERSION 11  /* 11: tmpc_ilqr_step_batch; 10: tmpc_*_solve_stream_device; 9: tmpc_pcg_dense_batch;
+#define TMPC_ABI_VERSION 11  /* 11: tmpc_ilqr_step_batch (later added, same version: tmpc_set_reference,
+                                tmpc_set_reference_device); 10: tmpc_*_solve_stream_device; 9: tmpc_pcg_dense_batch;
                                 8: tmpc_qp_blocks_batch */
 
 /* SQPSolverMethods (TrajoptMPCReference.py:13-18). */
@@ -209,6 +210,24 @@ int tmpc_set_box_limits(tmpc_ctx* ctx, const tmpc_box_limits* limits);
  * context across solves of the same (B, N), like the reference object's. */
 int tmpc_set_soft_state(tmpc_ctx* ctx, int B, int N, const double* mu, const double* lam, const double* phi);
 int tmpc_get_soft_state(tmpc_ctx* ctx, int B, int N, double* mu, double* lam, double* phi);
+
+/* Per-problem goals and per-knot reference trajectories for the following solves: xref [R][nx][M] (nx = 2 n,
+ * each row in the layout of x) replaces the cost's one goal xg in every QuadraticCost term.  One rule for every
+ * entry point:
+ *   - problem p tracks row p % R (a stream: p is the problem's index in the stream);
+ *   - knot k of MPC step s tracks column min(k + s, M - 1); batch and stream solves have s = 0.  So M = 1 is a
+ *     constant goal per problem, M >= N a per-knot reference, and the MPC loop slides its window one column per
+ *     step and holds the last column once the reference runs out;
+ *   - R must be 1 or the batch size B (tmpc_*_solve_batch*, tmpc_mpc_batch*, tmpc_qp_batch,
+ *     tmpc_ilqr_step_batch), 1 or stream.period (tmpc_*_solve_stream_device); a solve with another R fails.
+ * Only the state goal varies: Q, QF, R and QF_start stay the cost's.  The reference is copied into the context
+ * (tmpc_set_reference from host memory, tmpc_set_reference_device from device memory) and persists across solves,
+ * like the cost; R = 0 or a NULL array clears it, and so does tmpc_set_model (the reference needs a model: its
+ * rows have 2 n entries).  With no reference every solve is bit for bit what it is without these entry points; a
+ * reference whose columns all equal xg gives those same bits.  A solve with UrdfCost (tmpc_set_cost_ee) and a
+ * reference set fails: the task-space goal stays constant. */
+int tmpc_set_reference(tmpc_ctx* ctx, int R, int M, const double* xref);
+int tmpc_set_reference_device(tmpc_ctx* ctx, int R, int M, const double* d_xref);
 
 /* Batched TrajoptMPCReference.SQP (TrajoptMPCReference.py:510-760) for B independent problems,
  * with the soft-constraint outer loop (:483-508) when box limits are set.  x [B][nx][N] and u [B][nu][N-1] are read as the

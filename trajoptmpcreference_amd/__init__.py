@@ -7,14 +7,14 @@ interfaces; compute: hand-written gfx950 HIP kernels in libtmpc.so behind a
 ctypes C ABI (include/tmpc.h).  No CPU fallback.
 """
 from .constraint import BoxConstraint, TrajoptConstraint
-from .cost import QuadraticCost, TrajoptCost, UrdfCost
+from .cost import QuadraticCost, TrackingCost, TrajoptCost, UrdfCost
 from .pcg import PCG
 from .plant import PendulumPlant, TrajoptPlant, URDFPlant
 from .solver import MPCSolverMethods, SQPSolverMethods, TrajoptMPCReference
 from .urdf import RobotModel, parse_urdf, pendulum_urdf, planar_arm_urdf
 
 __all__ = [
-    "BoxConstraint", "TrajoptConstraint", "QuadraticCost", "TrajoptCost", "UrdfCost", "PCG", "TrajoptPlant", "URDFPlant",
+    "BoxConstraint", "TrajoptConstraint", "QuadraticCost", "TrackingCost", "TrajoptCost", "UrdfCost", "PCG", "TrajoptPlant", "URDFPlant",
     "PendulumPlant", "MPCSolverMethods", "SQPSolverMethods", "TrajoptMPCReference", "RobotModel", "parse_urdf",
     "pendulum_urdf", "planar_arm_urdf",
 ]

@@ -91,6 +91,8 @@ SIGNATURES = {
     "tmpc_default_options": (None, [C.POINTER(tmpc_options)]),
     "tmpc_set_options": (C.c_int, [C.c_void_p, C.POINTER(tmpc_options)]),
     "tmpc_set_box_limits": (C.c_int, [C.c_void_p, C.POINTER(tmpc_box_limits)]),
+    "tmpc_set_reference": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp]),
+    "tmpc_set_reference_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tmpc_set_soft_state": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp]),
     "tmpc_get_soft_state": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp]),
     "tmpc_sqp_solve_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _dp, _ip, _ip, _ip,
@@ -191,6 +193,20 @@ def _ptr(a):
     raise TypeError(a.dtype)
 
 
+def reference_array(goal, rows, nx, rows_name="batch size B"):
+    """A `goal=` argument as the reference xref [R][nx][M] of tmpc_set_reference: [R][nx] (a constant goal per
+    problem, M = 1) or [R][nx][M] (per-knot references), with R equal to 1 or `rows`.  Raises ValueError
+    otherwise; touches no device."""
+    g = np.asarray(goal, dtype=np.float64)
+    if g.ndim == 2:
+        g = g[:, :, None]
+    if g.ndim != 3 or g.shape[1] != nx or g.shape[2] < 1:
+        raise ValueError(f"goal must be [R][{nx}] or [R][{nx}][M] with M >= 1, got shape {np.shape(goal)}")
+    if g.shape[0] not in (1, rows):
+        raise ValueError(f"goal has R = {g.shape[0]} rows: must be 1 or the {rows_name} ({rows})")
+    return np.ascontiguousarray(g)
+
+
 def _c64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
@@ -267,6 +283,25 @@ class Context:
         self._check(self.lib.tmpc_set_cost_ee(self.h, self.nx, self.nu, _ptr(Q), _ptr(QF), _ptr(R), _ptr(xg),
                                               -1 if QF_start is None else int(QF_start), _ptr(H0), _ptr(Ha),
                                               _ptr(Hb)), "tmpc_set_cost_ee")
+
+    def set_reference(self, xref=None):
+        """Per-problem goals / per-knot reference trajectories for the following solves (tmpc_set_reference):
+        xref [R][nx][M] -- problem p tracks row p % R, knot k of MPC step s column min(k + s, M - 1); None
+        clears it (every solve then steers to the cost's xg)."""
+        if xref is None:
+            self._check(self.lib.tmpc_set_reference(self.h, 0, 0, None), "tmpc_set_reference")
+            return
+        xref = _c64(xref)
+        if xref.ndim != 3:
+            raise ValueError(f"xref must be [R][nx][M], got shape {xref.shape}")
+        if getattr(self, "model", None) is not None and xref.shape[1] != 2 * self.model.n:
+            raise ValueError(f"xref rows have {xref.shape[1]} entries, the model's state has {2 * self.model.n}")
+        self._check(self.lib.tmpc_set_reference(self.h, xref.shape[0], xref.shape[2], _ptr(xref)),
+                    "tmpc_set_reference")
+
+    def set_reference_device(self, R, M, d_xref):
+        """set_reference from device memory (tmpc_set_reference_device): d_xref [R][nx][M] doubles."""
+        self._check(self.lib.tmpc_set_reference_device(self.h, int(R), int(M), d_xref), "tmpc_set_reference_device")
 
     def set_options(self, **kw):
         for k, v in kw.items():
@@ -647,13 +682,17 @@ class Context:
             self._check(self.lib.tmpc_sqp_solve_stream_device(self.h, int(N), float(dt), LINSYS[solver], C.byref(st)),
                         "tmpc_sqp_solve_stream_device")
 
-    def solve_stream(self, x, u, N, dt, solver="PCG-SS", slots=64, copies=1, with_trace=True, substreams=1):
+    def solve_stream(self, x, u, N, dt, solver="PCG-SS", slots=64, copies=1, with_trace=True, substreams=1,
+                     goal=None):
         """Host convenience of solve_stream_device: problems x [P0][nx][N], u [P0][nu][N-1], each solved
         `copies` times (stream problem p = input p % P0) through `slots` slots.  Returns x, u [P][..],
-        status fields (exit, iters, exit_soft, outer_iter) [P] and the trace [P][max_iter+1]."""
+        status fields (exit, iters, exit_soft, outer_iter) [P] and the trace [P][max_iter+1].
+        goal: [P0][nx] or [P0][nx][M] (or one row for all) -- stream problem p tracks row p % P0; it is the
+        context's reference for this call only (set_reference), cleared afterwards."""
         x, u = _c64(x), _c64(u)
         self._check_traj(x, u, N)
         P0 = x.shape[0]
+        xref = None if goal is None else reference_array(goal, P0, x.shape[1], "stream's period")
         P = P0 * int(copies)
         W = int(self.options.max_iter_SQP_DDP) + 1
         bufs = []
@@ -667,6 +706,8 @@ class Context:
             self.h2d(dui, u)
             dxo, duo, dst = dev(x.nbytes * copies), dev(u.nbytes * copies), dev(P * 4 * 4)
             dtr = {name: dev(P * W * np.dtype(dt_).itemsize) for name, dt_ in TRACE_FIELDS} if with_trace else None
+            if xref is not None:
+                self.set_reference(xref)
             self.solve_stream_device(solver, P, slots, N, dt, dxi, dui, P0, dxo, duo, dst, dtr, substreams)
             xo = np.empty((P,) + x.shape[1:])
             uo = np.empty((P,) + u.shape[1:])
@@ -680,6 +721,8 @@ class Context:
                     trace[name] = np.empty((P, W), dtype=dt_)
                     self.d2h(trace[name], dtr[name])
         finally:
+            if xref is not None:
+                self.set_reference(None)
             for p in bufs:
                 self.free(p)
         return dict(x=xo, u=uo, exit=status[:, 0].copy(), iters=status[:, 1].copy(), exit_soft=status[:, 2].copy(),

@@ -85,6 +85,56 @@ class QuadraticCost(TrajoptCost):
         return self.QF_start
 
 
+class TrackingCost(QuadraticCost):
+    """QuadraticCost about a per-knot state reference xref [nx][M] (the layout of x) instead of one goal:
+    knot `timestep` measures x against column min(timestep + shift, M - 1), so M = 1 is a constant goal and
+    the reference holds its last column once it runs out.  `shift` is the receding-horizon offset:
+    shift_reference() advances it as shift_QF_start() moves QF_start, and MPC / MPC_batch do both per step.
+    Q, QF, R and QF_start are QuadraticCost's.  The GPU solver evaluates it on the device (the goal window,
+    csrc/tmpc_internal.h); these host hooks serve callers that evaluate costs themselves."""
+
+    def __init__(self, Q_in, QF_in, R_in, xref, QF_start=None):
+        xref = np.array(xref, dtype=np.float64)
+        if xref.ndim == 1:
+            xref = xref[:, None]
+        if xref.ndim != 2 or xref.shape[1] < 1:
+            raise ValueError(f"xref must be [nx][M] with M >= 1, got shape {xref.shape}")
+        super().__init__(Q_in, QF_in, R_in, xref[:, 0], QF_start)
+        if xref.shape[0] != self.Q.shape[0]:
+            raise ValueError(f"xref has {xref.shape[0]} rows, Q is {self.Q.shape[0]} x {self.Q.shape[0]}")
+        self.xref = xref
+        self.shift = 0
+
+    def goal(self, timestep=None):
+        """The goal of knot `timestep` (None: knot 0)."""
+        k = 0 if timestep is None else int(timestep)
+        return self.xref[:, min(k + self.shift, self.xref.shape[1] - 1)]
+
+    def window(self):
+        """The reference from the current shift on, [nx][M'] with M' >= 1: column k is knot k's goal."""
+        return self.xref[:, min(self.shift, self.xref.shape[1] - 1):]
+
+    def value(self, x, u=None, timestep=None, iter_1=0, iter_2=0, iter_3=0):
+        delta_x = np.asarray(x) - self.goal(timestep)
+        currQ = self.get_currQ(u, timestep)
+        cost = 0.5 * np.matmul(delta_x.transpose(), np.matmul(currQ, delta_x))
+        if u is not None:
+            u = np.asarray(u)
+            cost += 0.5 * np.matmul(u.transpose(), np.matmul(self.R, u))
+        return cost
+
+    def gradient(self, x, u=None, timestep=None, iter_1=0, iter_2=0, iter_3=0):
+        delta_x = np.asarray(x) - self.goal(timestep)
+        top = np.matmul(delta_x.transpose(), self.get_currQ(u, timestep))
+        if u is None:
+            return top
+        return np.hstack((top, np.matmul(np.asarray(u).transpose(), self.R)))
+
+    def shift_reference(self, steps: int = 1):
+        self.shift = max(self.shift + int(steps), 0)
+        return self.shift
+
+
 class UrdfCost(QuadraticCost):
     """End-effector cost (TrajoptCost.py:371-569): the quadratic form acts on the
     task state y = [p(q); J(q) qd] of the leaf's offset point [0, 1, 0, 1]

@@ -200,6 +200,8 @@ int tmpc_set_model(tmpc_ctx* ctx, int n, const int32_t* parent, const int32_t* j
   const char* gen = getenv("TMPC_GENERIC_MODEL");
   ctx->model_id = (gen && gen[0] == '1') ? 0 : match_static_model(m);
   ctx->soft_B = ctx->soft_N = -1;   // the soft-constraint state is sized per model (6 n slots per knot)
+  ctx->ref_dev = nullptr;           // and so is a state reference (nx rows)
+  ctx->ref_R = ctx->ref_M = 0;
   hipSetDevice(ctx->device);
   HIP_OK(hipMemcpyAsync(ctx->dmodel, &m, sizeof(m), hipMemcpyHostToDevice, ctx->stream));
   HIP_OK(hipStreamSynchronize(ctx->stream));
@@ -239,6 +241,35 @@ int tmpc_set_cost_ee(tmpc_ctx* ctx, int nx, int nu, const double* Q, const doubl
   memcpy(c.eeHa, Ha, sizeof(double) * 32);
   memcpy(c.eeHb, Hb, sizeof(double) * 32);
   return set_cost(ctx, c);
+}
+
+// The state reference xref [R][nx][M] (include/tmpc.h): copied into the context's own buffer, host or device source.
+static int set_reference(tmpc_ctx* ctx, int R, int M, const double* xref, hipMemcpyKind kind) {
+  if (!ctx) return -1;
+  if (R == 0 || !xref) {   // clear: every kernel reads the cost's xg again
+    ctx->ref_dev = nullptr;
+    ctx->ref_R = ctx->ref_M = 0;
+    return 0;
+  }
+  if (!ctx->has_model) return fail(ctx, "no model: call tmpc_set_model first (a reference has nx = 2 n rows)");
+  if (R < 1 || M < 1) return fail(ctx, "reference sizes R = %d, M = %d (both >= 1; R = 0 clears)", R, M);
+  hipSetDevice(ctx->device);
+  const size_t count = (size_t)R * 2 * ctx->hmodel.n * M;
+  BUF(double, ref_xref, count);
+  HIP_OK(hipMemcpyAsync(ref_xref, xref, count * sizeof(double), kind, ctx->stream));
+  HIP_OK(hipStreamSynchronize(ctx->stream));
+  ctx->ref_dev = ref_xref;
+  ctx->ref_R = R;
+  ctx->ref_M = M;
+  return 0;
+}
+
+int tmpc_set_reference(tmpc_ctx* ctx, int R, int M, const double* xref) {
+  return set_reference(ctx, R, M, xref, hipMemcpyHostToDevice);
+}
+
+int tmpc_set_reference_device(tmpc_ctx* ctx, int R, int M, const double* d_xref) {
+  return set_reference(ctx, R, M, d_xref, hipMemcpyDeviceToDevice);
 }
 
 void tmpc_default_options(tmpc_options* o) {

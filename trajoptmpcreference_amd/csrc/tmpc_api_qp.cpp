@@ -199,6 +199,7 @@ int tmpc_qp_batch(tmpc_ctx* ctx, int B, int N, double dt, int linsys, const doub
     w.hard = &hard;
   }
   ctx->hard_last = {0, 0, 0, 0, 0};
+  if ((rc = goal_window(ctx, B, N, B, "batch size", nullptr, 0, nullptr, &w.gw))) return rc;   // tmpc_set_reference
   if ((rc = run_qp(ctx, B, N, dt, precond, io_x, io_u, st, w, !banded, PList{nullptr, nullptr}, B)))
     return rc;
   HIP_OK(hipStreamSynchronize(ctx->stream));
@@ -257,6 +258,7 @@ int tmpc_ilqr_step_batch(tmpc_ctx* ctx, int B, int N, double dt, const double* x
   // xs = x[:, 0]: the trajectory is taken as given (no rollout), so the defects run_dynamics also forms are unused
   HIP_OK(hipMemcpy2DAsync(w.xs, sizeof(double), io_x, (size_t)N * sizeof(double), sizeof(double), (size_t)B * nx,
                           hipMemcpyDeviceToDevice, ctx->stream));
+  if ((rc = goal_window(ctx, B, N, B, "batch size", nullptr, 0, nullptr, &w.gw))) return rc;   // tmpc_set_reference
   if ((rc = ilqr_sweeps(ctx, N, dt, io_x, io_u, st, w, PList{nullptr, nullptr}, B, q))) return rc;
   HIP_OK(hipStreamSynchronize(ctx->stream));
   resolve_timings(ctx);

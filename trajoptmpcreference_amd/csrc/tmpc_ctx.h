@@ -67,6 +67,11 @@ struct tmpc_ctx {
   std::map<std::string, double> kbytes;   // bytes beyond registers / LDS of counting kernels since tmpc_reset_stats
   std::vector<tmpc_ctx*> subs;            // a stream's concurrent sub-streams (tmpc_stream.substreams): own HIP
                                           // stream and buffers each, the configuration copied from this context
+  // The state reference (tmpc_set_reference): xref [ref_R][nx][ref_M] on the device, ref_R = 0: none (every kernel
+  // reads CostDev::xg).  A sub-stream's context borrows its parent's array.  ref_step: the MPC step whose horizon
+  // solve runs (the window's first column; 0 outside mpc_device).
+  const double* ref_dev = nullptr;
+  int ref_R = 0, ref_M = 0, ref_step = 0;
 };
 
 namespace tmpc {
@@ -269,6 +274,7 @@ struct Work {
   double* Sg;                        // S / P^-1 rows in HBM past 1024 rows (k_qp<..., GM>), else null
   unsigned long long* tr_active;     // hard limits: per-QP active-set bitmasks into the trace (nullable)
   int Wtr;                           // trace row stride
+  double* gw;                        // the goal window [B][N][nx] of a tracking solve (goal_window), else null
 };
 
 int alloc_work(tmpc_ctx* ctx, int B, int N, Work& w, bool with_blocks);
@@ -309,5 +315,10 @@ int ilqr_device(tmpc_ctx* ctx, int B, int N, double dt, double* d_x, double* d_u
 int stream_solve(tmpc_ctx* ctx, int N, double dt, int linsys, const tmpc_stream* s);
 int mpc_device(tmpc_ctx* ctx, int B, int N, double dt, int solver, int steps, double* d_x, double* d_u,
                double* d_xe, double* d_ue, int* d_codes, int* d_iters);
+// The goal window of a horizon solve (tmpc_internal.h launch_goal_window): null without a reference.  What a
+// reference cannot be combined with (UrdfCost; R not 1 or `rows`, the batch size or the stream's period) is
+// refused here.  pid / pbase / mask: a stream's slots (null / 0 / null: problem b, every problem).
+int goal_window(tmpc_ctx* ctx, int B, int N, int rows, const char* rows_name, const int* pid, int pbase,
+                const int* mask, double** gw);
 
 }  // namespace tmpc

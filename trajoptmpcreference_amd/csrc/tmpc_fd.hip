@@ -73,7 +73,9 @@ __global__ void __launch_bounds__(256) k_qp_fd(MT M, PList P, int B, int N, doub
 // Two waves per SIMD (amdgpu_waves_per_eu(2)): left to itself the compiler took 256 VGPRs + 76 AGPRs, one
 // wave per SIMD, with nothing to hide the dynamics' latencies; at two it spills 348 B/lane and the headline
 // launch takes 0.142 ms instead of 0.195 (profiles/r04/ls_terms).
-template <int NJ, bool CHAIN, bool SOFT, class MT, class R>
+// TRK: the knot's state goal from the goal window gw [B][N][NX] (tmpc_set_reference) in place of C->xg -- one
+// contiguous run per lane whose address depends on (b, k) only, so it is issued with the knot's x / dx loads.
+template <int NJ, bool CHAIN, bool SOFT, class MT, class R, bool TRK>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k_ls_terms(MT M, const CostDev* __restrict__ C,
                                                   const ConstrDev* __restrict__ Cs, const double* __restrict__ mu,
                                                   const double* __restrict__ lam,
@@ -81,7 +83,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
                                                   const double* __restrict__ x, const double* __restrict__ u,
                                                   const double* __restrict__ xs, const double* __restrict__ dx,
                                                   const double* __restrict__ du, const int* __restrict__ active,
-                                                  double* __restrict__ terms) {
+                                                  double* __restrict__ terms, const double* __restrict__ gw) {
   constexpr int NX = 2 * NJ, NU = NJ;
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= B * T * N) return;
@@ -115,8 +117,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
     for (int m = 0; m < NX; ++m) Dk += gx[m] * dxk[m];
   } else {
   double d[NX];
+  const double* xg = TRK ? gw + ((size_t)b * N + k) * NX : C->xg;
 #pragma unroll
-  for (int m = 0; m < NX; ++m) d[m] = xk[m] - C->xg[m];
+  for (int m = 0; m < NX; ++m) d[m] = xk[m] - xg[m];
   // value: 0.5 dx^T (Q dx) [+ 0.5 u^T (R u)]; gradient: [dx^T Q, u^T R]
   double vq = 0.0;
   if (C->diag) {   // the same chains without their exact-zero terms (CostDev.diag)
@@ -363,13 +366,15 @@ struct LaunchFD {
   // chain, ModelRef, double> 19 kB per lane against 2.2 kB; 11.2 -> 1.9 ms per headline launch, DESIGN.md
   // 4a); the other FD kernels keep the chain instance, which measured faster for them
   static constexpr bool LCHAIN = MT::STATIC ? CHAIN : false;
+  // TRK: the tracking instances (a goal window gw), built in their own translation unit (tmpc_fd_trk.hip)
+  template <bool TRK>
   static void ls_terms(bool f32, hipStream_t s, const ModelDev* M, const CostDev* C, const ConstrDev* Cs, const double* mu,
                        const double* lam, PList P, int B, int N, int T, double dt, const double* alphas, const double* x,
                        const double* u, const double* xs, const double* dx, const double* du, const int* active,
-                       double* terms) {
+                       double* terms, const double* gw) {
 #define TMPC_LS(SOFTV, RV)                                                                                        \
-    hipLaunchKernelGGL((k_ls_terms<NJ, LCHAIN, SOFTV, MT, RV>), TMPC_GRID(B * T * N, 256), 0, s, MT::make(M), C, Cs, mu, \
-                       lam, P, B, N, T, dt, alphas, x, u, xs, dx, du, active, terms);
+    hipLaunchKernelGGL((k_ls_terms<NJ, LCHAIN, SOFTV, MT, RV, TRK>), TMPC_GRID(B * T * N, 256), 0, s, MT::make(M), C, Cs, \
+                       mu, lam, P, B, N, T, dt, alphas, x, u, xs, dx, du, active, terms, gw);
     if constexpr (kWide<NJ>) {   // a wide model: fp64 without soft limits only (check_ready refuses the rest)
       TMPC_LS(false, double)
     } else {
@@ -399,6 +404,18 @@ struct LaunchFD {
   }
 };
 
+#ifdef TMPC_TRK_PART
+int launch_ls_terms_trk(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, const CostDev* C,
+                        const ConstrDev* Cs, const double* mu, const double* lam, PList P, int B, int N, int T,
+                        double dt, const double* alphas, const double* x, const double* u, const double* xs,
+                        const double* dx, const double* du, const int* active, double* terms, const double* gw) {
+  return dispatch_model(mid, nj, chain, [&](auto t) {
+    using Tag = decltype(t);
+    LaunchFD<Tag::nj, Tag::chain, typename Tag::model>::template ls_terms<true>(f32, s, M, C, Cs, mu, lam, P, B, N, T, dt,
+                                                                                alphas, x, u, xs, dx, du, active, terms, gw);
+  });
+}
+#else
 int launch_qp_fd(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, PList P, int B, int N,
                  double dt, const double* x, const double* u, const double* xs, const int* need, double* qdd,
                  double* cvec) {
@@ -410,11 +427,15 @@ int launch_qp_fd(bool f32, hipStream_t s, int nj, bool chain, int mid, const Mod
 int launch_ls_terms(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, const CostDev* C,
                     const ConstrDev* Cs, const double* mu, const double* lam, PList P, int B, int N, int T, double dt,
                     const double* alphas, const double* x, const double* u, const double* xs, const double* dx,
-                    const double* du, const int* active, double* terms) {
+                    const double* du, const int* active, double* terms, const double* gw) {
+  if (gw)
+    return launch_ls_terms_trk(f32, s, nj, chain, mid, M, C, Cs, mu, lam, P, B, N, T, dt, alphas, x, u, xs, dx, du, active,
+                               terms, gw);
   return dispatch_model(mid, nj, chain, [&](auto t) {
     using Tag = decltype(t);
-    LaunchFD<Tag::nj, Tag::chain, typename Tag::model>::ls_terms(f32, s, M, C, Cs, mu, lam, P, B, N, T, dt, alphas, x, u,
-                                                                 xs, dx, du, active, terms);
+    LaunchFD<Tag::nj, Tag::chain, typename Tag::model>::template ls_terms<false>(f32, s, M, C, Cs, mu, lam, P, B, N, T, dt,
+                                                                                 alphas, x, u, xs, dx, du, active, terms,
+                                                                                 gw);
   });
 }
 int launch_unit_fd(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, int K, double dt,
@@ -439,5 +460,7 @@ int launch_mpc_shift(hipStream_t s, int nj, bool chain, int mid, const ModelDev*
     LaunchFD<T::nj, T::chain, typename T::model>::mpc_shift(s, M, B, N, dt, step, steps, x, u, xe, ue);
   });
 }
+
+#endif   // TMPC_TRK_PART
 
 }  // namespace tmpc

@@ -173,16 +173,18 @@ struct HGhat {
 };
 
 // the cost gradient g_k = [(x_k - xg)^T Q_k, u_k^T R] (+ soft jacobian; UrdfCost's x part in jsoft)
+// xg: the knot's state goal -- C->xg, or the knot's row of the goal window (k_hard_track_grad)
 template <int NJ>
-__device__ __forceinline__ double hard_grad(const CostDev* __restrict__ C, const double* xb, const double* ub,
-                                            const double* js, int N, int k, int c) {
+__device__ __forceinline__ double hard_grad(const CostDev* __restrict__ C, const double* __restrict__ xg,
+                                            const double* xb, const double* ub, const double* js, int N, int k,
+                                            int c) {
   constexpr int NX = 2 * NJ, NU = NJ;
   const int K = N - 1;
   double g = 0.0;
   if (c < NX) {
     if (C->kind == COST_EE) return js ? js[k * (NX + NU) + c] : 0.0;
     const double* Qk = h_use_QF(C, k, N) ? C->QF : C->Q;
-    for (int m = 0; m < NX; ++m) g += (xb[m * N + k] - C->xg[m]) * Qk[m * NX + c];
+    for (int m = 0; m < NX; ++m) g += (xb[m * N + k] - xg[m]) * Qk[m * NX + c];
   } else if (k < K) {
     for (int m = 0; m < NU; ++m) g += ub[m * K + k] * C->R[m * NU + (c - NX)];
   }
@@ -306,7 +308,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) k
   // phase 0: the cost gradient of every knot (0 for the terminal knot's u part)
   for (int e = threadIdx.x; e < N * NXU; e += blockDim.x) {
     const int k = e / NXU, m = e - k * NXU;
-    s_grad[e] = (m < NX || k < K) ? (gvec ? gvec[(size_t)b * N * NXU + e] : hard_grad<NJ>(C, xb, ub, js, N, k, m))
+    s_grad[e] = (m < NX || k < K) ? (gvec ? gvec[(size_t)b * N * NXU + e] : hard_grad<NJ>(C, C->xg, xb, ub, js, N, k, m))
                                   : 0.0;
   }
   __syncthreads();
@@ -1331,7 +1333,7 @@ __global__ void __launch_bounds__(64) k_hard_dxu(const CostDev* __restrict__ C, 
   double rhs[3 * NJ];
 #pragma unroll
   for (int m = 0; m < NXU; ++m)
-    rhs[m] = (m < NX || k < K) ? (gvec ? gvec[((size_t)b * N + k) * NXU + m] : hard_grad<NJ>(C, xb, ub, js, N, k, m))
+    rhs[m] = (m < NX || k < K) ? (gvec ? gvec[((size_t)b * N + k) * NXU + m] : hard_grad<NJ>(C, C->xg, xb, ub, js, N, k, m))
                                      - ctl[m]
                                : 0.0;
   if (per_knot == 2) {   // the plugin-hook QP's full block (k_ghat_full): dxu_k = Ghat_k (g_k - (C^T lambda)_k)
@@ -1489,6 +1491,35 @@ int hard_set_max_lds() {
     set(k_hard_pcg<NX, 4>);
   });
   return err;
+}
+
+// The banded QP of a tracking solve (tmpc_set_reference): hard_grad against the goal window, for every knot of
+// every active problem, into gvec [B][N][NX + NU] -- the caller's-gradient input k_hard_schur / k_hard_dxu already
+// have (the plugin-hook QP's), so those kernels are the fixed-goal solve's, untouched.
+template <int NJ>
+__global__ void __launch_bounds__(256) k_hard_track_grad(const CostDev* __restrict__ C, int B, int N,
+                                                         const int* __restrict__ active, const double* __restrict__ x,
+                                                         const double* __restrict__ u, const double* __restrict__ jsoft,
+                                                         const double* __restrict__ gw, double* __restrict__ gvec) {
+  constexpr int NX = 2 * NJ, NU = NJ, NXU = NX + NU;
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= B * N * NXU) return;
+  const int b = gid / (N * NXU), e = gid - b * (N * NXU);
+  if (!active[b]) return;
+  const int k = e / NXU, m = e - k * NXU;
+  const double* js = jsoft ? jsoft + (size_t)b * N * NXU : nullptr;
+  gvec[gid] = (m < NX || k < N - 1)
+                  ? hard_grad<NJ>(C, gw + ((size_t)b * N + k) * NX, x + (size_t)b * NX * N, u + (size_t)b * NU * (N - 1),
+                                  js, N, k, m)
+                  : 0.0;
+}
+
+int launch_hard_track_grad(hipStream_t s, int nj, const HardArgs& h, const double* gw, double* gvec) {
+  return for_nj<1, NJ_FULL>(nj, [&](auto n) {
+    constexpr int NJ = decltype(n)::value;
+    hipLaunchKernelGGL((k_hard_track_grad<NJ>), TMPC_GRID(h.B * h.N * 3 * NJ, 256), 0, s, h.C, h.B, h.N, h.active, h.x,
+                       h.u, h.jsoft, gw, gvec);
+  });
 }
 
 }  // namespace tmpc

@@ -27,7 +27,7 @@ __device__ __forceinline__ bool use_QF(const CostDev* C, int k, int N) {
 }
 
 // ======================================================================= backward (Riccati) sweep
-template <int NJ, class R>
+template <int NJ, class R, bool TRK = false>
 struct IlqrLds {
   static constexpr int NX = 2 * NJ, NU = NJ;
   R Vxx[NX * NX], Vx[NX];
@@ -37,7 +37,7 @@ struct IlqrLds {
   R KD[NU * (NX + 1)];                  // [Q_uu^-1 Q_ux | Q_uu^-1 Q_u], row-major
   R lx[NX], lu[NU], jac[3 * NJ];
   R Q[NX * NX], QF[NX * NX], Rc[NU * NU];   // the cost's Hessian blocks, staged once
-  double xg[NX];
+  double xg[TRK ? 2 : 1][NX];           // the goal; TRK: knot k's and the prefetched knot's, in z's slots
   double z[2][NX + NU];                 // knot k's [x_k; u_k] and the prefetched knot's (fp64: the soft terms)
   int fail;
   R trash[64];                          // the stores of lanes without an output land here
@@ -81,7 +81,10 @@ __device__ __forceinline__ float lane_val(float v, int l) {
 // is the same products summed in the same order as the VALU loops.
 typedef double dbl4 __attribute__((ext_vector_type(4)));
 
-template <int NJ, class R, bool MF>
+// TRK: per-knot goals from the goal window gw [B][N][NX] (tmpc_set_reference).  Knot k - 1's goal is loaded with
+// that knot's A, B, x, u prefetch (one entry per lane, like z) and lands in LDS beside z at the end of knot k, so
+// the serial chain never waits for it.
+template <int NJ, class R, bool MF, bool TRK = false>
 __global__ void __launch_bounds__(64) k_ilqr_backward(const CostDev* __restrict__ C, const ConstrDev* __restrict__ Cs,
                                                       PList P, int B, int N, const double* __restrict__ x,
                                                       const double* __restrict__ u, const double* __restrict__ rho_in,
@@ -90,13 +93,13 @@ __global__ void __launch_bounds__(64) k_ilqr_backward(const CostDev* __restrict_
                                                       const double* __restrict__ lam,
                                                       const double* __restrict__ jsoft, double* __restrict__ Kout,
                                                       double* __restrict__ dout, double* __restrict__ dV,
-                                                      int* __restrict__ ok) {
+                                                      int* __restrict__ ok, const double* __restrict__ gw) {
   constexpr int NX = 2 * NJ, NU = NJ, NC = NX + 1;
   constexpr int NA = (NX * NX + 63) / 64, NB = (NX * NU + 63) / 64;   // prefetch slots per lane
   if (!P.has(blockIdx.x, B)) return;
   const int b = P.at(blockIdx.x);
   if (!active[b]) return;
-  __shared__ IlqrLds<NJ, R> L;
+  __shared__ IlqrLds<NJ, R, TRK> L;
   const int t = threadIdx.x;
   const int K = N - 1;
   const R rho = R(rho_in[b]);
@@ -112,7 +115,9 @@ __global__ void __launch_bounds__(64) k_ilqr_backward(const CostDev* __restrict_
     L.QF[e] = R(C->QF[e]);
   }
   for (int e = t; e < NU * NU; e += 64) L.Rc[e] = R(C->R[e]);
-  if (t < NX) L.xg[t] = C->xg[t];
+  if (!TRK && t < NX) L.xg[0][t] = C->xg[t];
+  // TRK: this lane's entry of a knot's goal
+  auto load_g = [&](int k) -> double { return (TRK && t < NX) ? gw[((size_t)b * N + k) * NX + t] : 0.0; };
   auto use_qf = [&](int k) { return (k == N - 1) || (qf_start >= 0 && k >= qf_start); };
   // [x_k; u_k] of a knot, one entry per lane (u_{N-1} := 0)
   auto load_z = [&](int k) -> double {
@@ -153,6 +158,7 @@ __global__ void __launch_bounds__(64) k_ilqr_backward(const CostDev* __restrict_
   auto stage_l = [&](int k, int zs, double zr) {
     const bool term = k == K;
     const double* zk = L.z[zs];
+    const double* xgk = L.xg[TRK ? zs : 0];
     const R jt = R(pj);                  // this lane's entry of the knot's soft-limit jacobian
     if (t < 3 * NJ) L.jac[t] = jt;       // 0 without soft limits
     // lanes < NX: l_x[t], lanes NX .. NX + NU - 1: l_u[t - NX].  Both dot products on every lane and
@@ -168,7 +174,7 @@ __global__ void __launch_bounds__(64) k_ilqr_backward(const CostDev* __restrict_
       // row sum (0 * inf) is raised by a ballot over the wave (diag_poison's rule)
       const int tq = t < NX ? t : 0;
       const R qdg = (use_qf(k) ? L.QF : L.Q)[tq * NX + tq], rdg = L.Rc[tu * NU + tu];
-      const R yt = R(zr - L.xg[tq]), wt = R(zr);
+      const R yt = R(zr - xgk[tq]), wt = R(zr);
       const bool badx = __ballot(t < NX && !isfinite(yt)) != 0;
       const bool badu = __ballot(isu && !isfinite(wt)) != 0;
       g = fma_r(yt, qdg, R(0)) + ((badx && NX > 1) ? R(NAN) : R(0));
@@ -177,7 +183,7 @@ __global__ void __launch_bounds__(64) k_ilqr_backward(const CostDev* __restrict_
       wave_lds_sync();
       const R* Qk = use_qf(k) ? L.QF : L.Q;
 #pragma unroll
-      for (int m = 0; m < NX; ++m) g += R(zk[m] - L.xg[m]) * Qk[m * NX + tx];
+      for (int m = 0; m < NX; ++m) g += R(zk[m] - xgk[m]) * Qk[m * NX + tx];
 #pragma unroll
       for (int m = 0; m < NU; ++m) gu += R(zk[NX + m]) * L.Rc[m * NU + tu];
     }
@@ -202,7 +208,9 @@ __global__ void __launch_bounds__(64) k_ilqr_backward(const CostDev* __restrict_
     load_ab(K - 1);
     pjn = load_jac(K - 1);
     const double zn = load_z(K - 1);
+    const double gt = load_g(K), gn = load_g(K - 1);
     if (t < NX + NU) L.z[0][t] = zt;
+    if (TRK && t < NX) L.xg[0][t] = gt;
     wave_lds_sync();
     stage_l(K, 0, zt);
     wave_lds_sync();
@@ -213,6 +221,7 @@ __global__ void __launch_bounds__(64) k_ilqr_backward(const CostDev* __restrict_
     }
     store_ab(0);
     if (t < NX + NU) L.z[1][t] = zn;
+    if (TRK && t < NX) L.xg[TRK ? 1 : 0][t] = gn;
     zr = zn;
     pj = pjn;
     wave_lds_sync();
@@ -227,11 +236,12 @@ __global__ void __launch_bounds__(64) k_ilqr_backward(const CostDev* __restrict_
     const R* A = L.A[cur];
     const R* Bm = L.Bm[cur];
     // next knot's A, B, z: loads issued now, written to the other slot at the end of this knot
-    double zn = 0.0;
+    double zn = 0.0, gn = 0.0;
     if (k > 0) {
       load_ab(k - 1);
       pjn = load_jac(k - 1);
       zn = load_z(k - 1);
+      gn = load_g(k - 1);
     }
     stage_l(k, 1 - cur, zr);
     wave_lds_sync();
@@ -505,6 +515,7 @@ __global__ void __launch_bounds__(64) k_ilqr_backward(const CostDev* __restrict_
     if (k > 0) {
       store_ab(1 - cur);
       if (t < NX + NU) L.z[cur][t] = zn;
+      if (TRK && t < NX) L.xg[TRK ? cur : 0][t] = gn;
       zr = zn;
       pj = pjn;
     }
@@ -526,15 +537,16 @@ __global__ void __launch_bounds__(64) k_ilqr_backward(const CostDev* __restrict_
 
 // QuadraticCost.value of one knot (TrajoptCost.py:49-56): 0.5 dx^T (Q dx) [+ 0.5 u^T (R u)], one
 // expression shared by the rollouts and the INIT evaluation so both round alike
-template <int NJ>
-__device__ __forceinline__ double knot_quad_cost(const CostDev* __restrict__ C, int k, int N, const double* xh,
-                                                 const double* uh, bool term) {
+// TRK: the knot's state goal is its row xg of the goal window; else C->xg, read here as it always was (xg unused)
+template <int NJ, bool TRK = false>
+__device__ __forceinline__ double knot_quad_cost(const CostDev* __restrict__ C, const double* xg, int k, int N,
+                                                 const double* xh, const double* uh, bool term) {
   constexpr int NX = 2 * NJ, NU = NJ;
   const double* Qk = use_QF(C, k, N) ? C->QF : C->Q;
   if (C->diag) {   // the same chains without their exact-zero terms (CostDev.diag)
     double y[NX];
 #pragma unroll
-    for (int r = 0; r < NX; ++r) y[r] = xh[r] - C->xg[r];
+    for (int r = 0; r < NX; ++r) y[r] = xh[r] - (TRK ? xg[r] : C->xg[r]);
     double vq = 0.0;
 #pragma unroll
     for (int r = 0; r < NX; ++r) vq = __fma_rn(y[r], __fma_rn(Qk[r * NX + r], y[r], 0.0), vq);
@@ -552,8 +564,8 @@ __device__ __forceinline__ double knot_quad_cost(const CostDev* __restrict__ C, 
   for (int r = 0; r < NX; ++r) {
     double qd = 0.0;
 #pragma unroll
-    for (int c = 0; c < NX; ++c) qd += Qk[r * NX + c] * (xh[c] - C->xg[c]);
-    vq += (xh[r] - C->xg[r]) * qd;
+    for (int c = 0; c < NX; ++c) qd += Qk[r * NX + c] * (xh[c] - (TRK ? xg[c] : C->xg[c]));
+    vq += (xh[r] - (TRK ? xg[r] : C->xg[r])) * qd;
   }
   double cost = 0.5 * vq;
   if (!term) {
@@ -576,12 +588,12 @@ __device__ __forceinline__ double knot_quad_cost(const CostDev* __restrict__ C, 
 // totalCost's order (:296-310) and the serial sums of k_ilqr_forward operand for operand.  Run
 // under the act_init mask every outer-loop iteration, so it must be cheap when few problems
 // restart (the serial INIT rollout lane took 0.19 ms per launch on average).
-template <int NJ, bool SOFT>
+template <int NJ, bool SOFT, bool TRK = false>
 __global__ void __launch_bounds__(64) k_ilqr_init_cost(const CostDev* __restrict__ C, const ConstrDev* __restrict__ Cs,
                                                        const double* __restrict__ mu, const double* __restrict__ lam,
                                                        PList P, int B, int N, const double* __restrict__ x,
                                                        const double* __restrict__ u, const int* __restrict__ mask,
-                                                       double* __restrict__ Jt) {
+                                                       double* __restrict__ Jt, const double* __restrict__ gw) {
   constexpr int NX = 2 * NJ, NU = NJ;
   if (!P.has(blockIdx.x, B)) return;
   const int b = P.at(blockIdx.x);
@@ -597,7 +609,7 @@ __global__ void __launch_bounds__(64) k_ilqr_init_cost(const CostDev* __restrict
     for (int m = 0; m < NX; ++m) xh[m] = xb[m * N + k];
 #pragma unroll
     for (int i = 0; i < NU; ++i) uh[i] = term ? 0.0 : ub[i * K + k];
-    sc[k] = knot_quad_cost<NJ>(C, k, N, xh, uh, term);
+    sc[k] = knot_quad_cost<NJ, TRK>(C, TRK ? gw + ((size_t)b * N + k) * NX : nullptr, k, N, xh, uh, term);
     if (SOFT) {
       double z[3 * NJ], jac[3 * NJ];
 #pragma unroll
@@ -630,11 +642,14 @@ __global__ void __launch_bounds__(64) k_ilqr_init_cost(const CostDev* __restrict
 // LDS-DMA (global_load_lds: no VGPRs, the kernel is at the register cap) while this knot's
 // dynamics run.  Per problem and knot: K_k in 16-byte pieces, then d_k, x_k, u_k in dwords
 // (x / u are strided by knot in the reference layout).  Buffer [2][nprob][SK + SS] doubles.
-template <int NJ>
+// TRK (tmpc_set_reference): knot k's goal, one contiguous row of the knot-major goal window, rides the same
+// dword stream after u_k.
+template <int NJ, bool TRK = false>
 struct FwdPf {
   static constexpr int NX = 2 * NJ, NU = NJ;
   static constexpr int SK = NU * NX;            // K_k
-  static constexpr int SS = NU + NX + NU;       // d_k, x_k, u_k
+  static constexpr int SG = NU + NX + NU;       // where the goal starts
+  static constexpr int SS = SG + (TRK ? NX : 0);   // d_k, x_k, u_k (, goal_k)
   static constexpr int CK = SK / 2;             // 16-byte pieces of K_k (SK is even)
   static __host__ __device__ int nprob(int T) { return 63 / T + 2; }   // problems a 64-lane group can touch
   // regions rounded up to whole wave-instructions (64 x 16 B, 64 x 4 B): the last instruction's
@@ -650,7 +665,10 @@ struct FwdPf {
 // LDS-DMA may alias them -- exposing the DMA's latency), explicit waits after the loads into xh / uh, the
 // DMA sources precomputed, the knot's wait through the builtin:
 // ilqr_forward 0.472 -> 0.401 ms per launch, config 3 4.37k -> 4.65k solves/s
-template <int NJ, bool CHAIN, bool SOFT, class MT, class R, bool PF>
+// TRK: the goal of knots 0 .. K - 1 arrives with that prefetch; the terminal knot's (no feedback law, so no
+// prefetch) and the plain instance's are read from the window directly, at addresses the rollout does not
+// feed -- one wait per rollout, not one per knot.
+template <int NJ, bool CHAIN, bool SOFT, class MT, class R, bool PF, bool TRK = false>
 __global__ void __launch_bounds__(64) k_ilqr_forward(MT Mg, const CostDev* __restrict__ C,
                                                      const ConstrDev* __restrict__ Cs, const double* __restrict__ mu,
                                                      const double* __restrict__ lam, PList P, int B, int N, int T,
@@ -659,13 +677,13 @@ __global__ void __launch_bounds__(64) k_ilqr_forward(MT Mg, const CostDev* __res
                                                      const double* __restrict__ Kg, const double* __restrict__ dg,
                                                      const int* __restrict__ active, const int* __restrict__ ok,
                                                      double* __restrict__ xt, double* __restrict__ ut,
-                                                     double* __restrict__ Jt) {
+                                                     double* __restrict__ Jt, const double* __restrict__ gw) {
   // the runtime model is staged in LDS (tmpc_device.h, stage_model); compiled models need no data
   __shared__ ModelDev sM;
   MT M = Mg;
   if constexpr (!MT::STATIC) M = ModelRef{stage_model(Mg.p, &sM)};
   constexpr int NX = 2 * NJ, NU = NJ;
-  using PF_ = FwdPf<NJ>;
+  using PF_ = FwdPf<NJ, TRK>;
   extern __shared__ __align__(16) double pfb[];
   const int lane = threadIdx.x;
   const int gid = blockIdx.x * blockDim.x + lane;
@@ -686,6 +704,7 @@ __global__ void __launch_bounds__(64) k_ilqr_forward(MT Mg, const CostDev* __res
   const double al = init ? 0.0 : alphas[tr];
   const double* xb = x + (size_t)b * NX * N;
   const double* ub = u + (size_t)b * NU * K;
+  const double* gwb = TRK ? gw + (size_t)b * N * NX : nullptr;   // this problem's goals [N][NX]
   const size_t bt = (size_t)b * T + tr;   // this lane's trial slot
   double* xo = xt + bt * NX * N;
   double* uo = ut + bt * NU * K;
@@ -725,9 +744,10 @@ __global__ void __launch_bounds__(64) k_ilqr_forward(MT Mg, const CostDev* __res
       const int bs = s_pb[min(ps, npt - 1)];
       const double* src = item < NU ? dg + (size_t)bs * K * NU + item
                         : item < NU + NX ? x + ((size_t)bs * NX + (item - NU)) * N
-                                         : u + ((size_t)bs * NU + (item - NU - NX)) * K;
+                        : (!TRK || item < PF_::SG) ? u + ((size_t)bs * NU + (item - NU - NX)) * K
+                                                   : gw + (size_t)bs * N * NX + (item - PF_::SG);
       sbase[j] = (const char*)src + 4 * half;
-      sstride[j] = item < NU ? NU * 8 : 8;
+      sstride[j] = item < NU ? NU * 8 : (!TRK || item < PF_::SG) ? 8 : NX * 8;
     }
   }
   auto prefetch = [&](int kn, int slot) {
@@ -764,7 +784,8 @@ __global__ void __launch_bounds__(64) k_ilqr_forward(MT Mg, const CostDev* __res
       const int bb = s_pb[min(p, npt - 1)];
       const double* src = item < NU ? dg + ((size_t)bb * K + kn) * NU + item
                         : item < NU + NX ? x + ((size_t)bb * NX + (item - NU)) * N + kn
-                                         : u + ((size_t)bb * NU + (item - NU - NX)) * K + kn;
+                        : (!TRK || item < PF_::SG) ? u + ((size_t)bb * NU + (item - NU - NX)) * K + kn
+                                                   : gw + ((size_t)bb * N + kn) * NX + (item - PF_::SG);
       __builtin_amdgcn_global_load_lds((const char*)src + 4 * half,
                                        (__attribute__((address_space(3))) void*)(sb + (size_t)j * 32), 4, 0, 0);
     }
@@ -786,6 +807,7 @@ __global__ void __launch_bounds__(64) k_ilqr_forward(MT Mg, const CostDev* __res
     IL_STAMP(7);
     const bool term = k == K;
     double uh[NU];
+    double gh[TRK ? NX : 1];   // TRK: the knot's goal
     if (pf && !term) {
       // knot k's operands have landed in LDS.  The wait goes through the builtin, which is no
       // compiler memory barrier (an asm's "memory" clobber made every knot reload the cost's
@@ -803,6 +825,14 @@ __global__ void __launch_bounds__(64) k_ilqr_forward(MT Mg, const CostDev* __res
 #pragma unroll
       for (int m = 0; m < NX; ++m) xh[m] = xb[m * N + k];
       __builtin_amdgcn_s_waitcnt(0x0F70);
+    }
+    if constexpr (TRK) {
+      if (term || !pf) {
+#pragma unroll
+        for (int m = 0; m < NX; ++m) gh[m] = gwb[(size_t)k * NX + m];
+        // prefetching instance: the terminal knot only, waited for here as the loads into xh / uh are (above)
+        if (pf) __builtin_amdgcn_s_waitcnt(0x0F70);
+      }
     }
     if (!term) {
       if (init) {
@@ -823,6 +853,10 @@ __global__ void __launch_bounds__(64) k_ilqr_forward(MT Mg, const CostDev* __res
 #pragma unroll
         for (int m = 0; m < NX; ++m) kr[0][m] = Kk[m];
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (TRK) {
+#pragma unroll
+          for (int m = 0; m < NX; ++m) gh[m] = sv[PF_::SG + m];
+        }
         double dx[NX];
 #pragma unroll
         for (int m = 0; m < NX; ++m) dx[m] = xh[m] - sv[NU + m];
@@ -857,7 +891,7 @@ __global__ void __launch_bounds__(64) k_ilqr_forward(MT Mg, const CostDev* __res
     if (pf && k + 1 < K) prefetch(k + 1, (k + 1) & 1);
     if (live) {
     IL_STAMP(0);
-    J = J + knot_quad_cost<NJ>(C, k, N, xh, uh, term);
+    J = J + knot_quad_cost<NJ, TRK>(C, TRK ? gh : nullptr, k, N, xh, uh, term);
     IL_STAMP(1);
     if (!term && !init) {
       double qd[NJ], qdd[NJ];
@@ -1004,6 +1038,7 @@ __global__ void __launch_bounds__(256) k_ilqr_soft_jac(const ConstrDev* __restri
 // One 64-lane workgroup per problem.  Acceptance ratio (J - J^) / (-alpha (dV1 + alpha dV2)) in
 // [exp_red_min, exp_red_max] in the reference's alpha order (oracle/ilqr.py), rho schedule and exit
 // codes of reduce_regularization / check_for_exit_or_error (:457-481), trace row, trajectory copy.
+#ifndef TMPC_TRK_PART   // (not a template: in the fixed-goal translation unit only)
 __global__ void __launch_bounds__(64) k_ilqr_decide(PList P, int B, int N, int NX, int NU, int T, int init,
                                                     const double* __restrict__ alphas, SolverOpts o,
                                                     const double* __restrict__ Jt, const double* __restrict__ dV,
@@ -1125,18 +1160,24 @@ __global__ void __launch_bounds__(64) k_ilqr_decide(PList P, int B, int N, int N
   }
 }
 
+#endif   // TMPC_TRK_PART
+
 // ======================================================================= launchers
 
 // the backward sweep and the initial cost depend on the joint count only
 template <int NJ>
 struct LaunchIlqrNJ {
+  // TRK: the tracking instances (a goal window gw), built in their own translation unit (tmpc_ilqr_trk.hip)
+  template <bool TRK>
   static void backward(bool f32, hipStream_t s, const CostDev* C, const ConstrDev* Cs, PList P, int B, int N, const double* x,
                        const double* u, const double* rho, const int* active, const double* A, const double* Bm,
                        const double* mu, const double* lam, double* jscratch, double* K, double* d, double* dV,
-                       int* ok) {
+                       int* ok, const double* gw) {
+#define TMPC_BWD(RV, MFV, JS)                                                                                          \
+    hipLaunchKernelGGL((k_ilqr_backward<NJ, RV, MFV, TRK>), dim3(B), dim3(64), 0, s, C, Cs, P, B, N, x, u, rho, active, A, \
+                       Bm, mu, lam, JS, K, d, dV, ok, gw);
     if constexpr (kWide<NJ>) {   // a wide model: fp64 VALU sweep, no soft limits (check_ready refuses the rest)
-      hipLaunchKernelGGL((k_ilqr_backward<NJ, double, false>), dim3(B), dim3(64), 0, s, C, Cs, P, B, N, x, u, rho, active,
-                         A, Bm, mu, lam, nullptr, K, d, dV, ok);
+      TMPC_BWD(double, false, nullptr)
     } else {
       // fp64: the matrix-core products (MF) unless TMPC_ILQR_VALU=1 (the VALU loops, for comparison)
       const char* v = getenv("TMPC_ILQR_VALU");
@@ -1151,56 +1192,55 @@ struct LaunchIlqrNJ {
       // accumulation, rounded to fp32) unless TMPC_ILQR_F32_VALU=1 (the fp32 VALU loops)
       const char* fv = getenv("TMPC_ILQR_F32_VALU");
       const bool f32mf = mf && !(fv && fv[0] == '1');
-      if (f32 && f32mf)
-        hipLaunchKernelGGL((k_ilqr_backward<NJ, float, true>), dim3(B), dim3(64), 0, s, C, Cs, P, B, N, x, u, rho, active, A,
-                           Bm, mu, lam, js, K, d, dV, ok);
-      else if (f32)
-        hipLaunchKernelGGL((k_ilqr_backward<NJ, float, false>), dim3(B), dim3(64), 0, s, C, Cs, P, B, N, x, u, rho, active, A,
-                           Bm, mu, lam, js, K, d, dV, ok);
-      else if (mf)
-        hipLaunchKernelGGL((k_ilqr_backward<NJ, double, true>), dim3(B), dim3(64), 0, s, C, Cs, P, B, N, x, u, rho, active, A,
-                           Bm, mu, lam, js, K, d, dV, ok);
-      else
-        hipLaunchKernelGGL((k_ilqr_backward<NJ, double, false>), dim3(B), dim3(64), 0, s, C, Cs, P, B, N, x, u, rho, active, A,
-                           Bm, mu, lam, js, K, d, dV, ok);
+      if (f32 && f32mf) { TMPC_BWD(float, true, js) }
+      else if (f32) { TMPC_BWD(float, false, js) }
+      else if (mf) { TMPC_BWD(double, true, js) }
+      else { TMPC_BWD(double, false, js) }
     }
+#undef TMPC_BWD
   }
+  template <bool TRK>
   static void init_cost(hipStream_t s, const CostDev* C, const ConstrDev* Cs, const double* mu, const double* lam, PList P,
-                        int B, int N, const double* x, const double* u, const int* mask, double* Jt) {
+                        int B, int N, const double* x, const double* u, const int* mask, double* Jt, const double* gw) {
     const size_t lds = (size_t)2 * N * sizeof(double);
+#define TMPC_INITC(SOFTV)                                                                                              \
+    hipLaunchKernelGGL((k_ilqr_init_cost<NJ, SOFTV, TRK>), dim3(B), dim3(64), lds, s, C, Cs, mu, lam, P, B, N, x, u, mask, \
+                       Jt, gw);
     if constexpr (!kWide<NJ>) {   // a wide model: no soft limits (launch_ilqr_init_cost refuses them)
       if (mu) {
-        hipLaunchKernelGGL((k_ilqr_init_cost<NJ, true>), dim3(B), dim3(64), lds, s, C, Cs, mu, lam, P, B, N, x, u, mask, Jt);
+        TMPC_INITC(true)
         return;
       }
     }
-    hipLaunchKernelGGL((k_ilqr_init_cost<NJ, false>), dim3(B), dim3(64), lds, s, C, Cs, mu, lam, P, B, N, x, u, mask, Jt);
+    TMPC_INITC(false)
+#undef TMPC_INITC
   }
 };
 
 template <int NJ, bool CHAIN, class MT>
 struct LaunchIlqr {
+  template <bool TRK>
   static void forward(bool f32, hipStream_t s, const ModelDev* M, const CostDev* C, const ConstrDev* Cs, const double* mu,
                       const double* lam, PList P, int B, int N, int T, double dt, int init, const double* alphas,
                       const double* x, const double* u, const double* K, const double* d, const int* active,
-                      const int* ok, double* xt, double* ut, double* Jt) {
+                      const int* ok, double* xt, double* ut, double* Jt, const double* gw) {
     // the prefetching instance when its LDS buffers fit (T >= 2: <= 33 problems per group); init
     // evaluations (no feedback law) take the plain one.  TMPC_ILQR_NOPF=1: plain only (comparison)
     const char* npf = getenv("TMPC_ILQR_NOPF");
-    const size_t pf_lds = FwdPf<NJ>::lds_doubles(T) * sizeof(double);
+    const size_t pf_lds = FwdPf<NJ, TRK>::lds_doubles(T) * sizeof(double);
     const bool pf = !init && pf_lds <= 48 * 1024 && !(npf && npf[0] == '1');
     if constexpr (kWide<NJ>) {   // a wide model: fp64, no soft limits, the plain (non-prefetching) instance
-      hipLaunchKernelGGL((k_ilqr_forward<NJ, CHAIN, false, MT, double, false>), TMPC_GRID(B * T, 64), 0, s, MT::make(M), C,
-                         Cs, mu, lam, P, B, N, T, dt, init, alphas, x, u, K, d, active, ok, xt, ut, Jt);
+      hipLaunchKernelGGL((k_ilqr_forward<NJ, CHAIN, false, MT, double, false, TRK>), TMPC_GRID(B * T, 64), 0, s,
+                         MT::make(M), C, Cs, mu, lam, P, B, N, T, dt, init, alphas, x, u, K, d, active, ok, xt, ut, Jt, gw);
       return;
     } else {
 #define TMPC_FWD(SOFTV, RV)                                                                                          \
     if (pf)                                                                                                          \
-      hipLaunchKernelGGL((k_ilqr_forward<NJ, CHAIN, SOFTV, MT, RV, true>), TMPC_GRID(B * T, 64), pf_lds, s,           \
-                         MT::make(M), C, Cs, mu, lam, P, B, N, T, dt, init, alphas, x, u, K, d, active, ok, xt, ut, Jt); \
+      hipLaunchKernelGGL((k_ilqr_forward<NJ, CHAIN, SOFTV, MT, RV, true, TRK>), TMPC_GRID(B * T, 64), pf_lds, s,      \
+                         MT::make(M), C, Cs, mu, lam, P, B, N, T, dt, init, alphas, x, u, K, d, active, ok, xt, ut, Jt, gw); \
     else                                                                                                             \
-      hipLaunchKernelGGL((k_ilqr_forward<NJ, CHAIN, SOFTV, MT, RV, false>), TMPC_GRID(B * T, 64), 0, s, MT::make(M),  \
-                         C, Cs, mu, lam, P, B, N, T, dt, init, alphas, x, u, K, d, active, ok, xt, ut, Jt);
+      hipLaunchKernelGGL((k_ilqr_forward<NJ, CHAIN, SOFTV, MT, RV, false, TRK>), TMPC_GRID(B * T, 64), 0, s, MT::make(M), \
+                         C, Cs, mu, lam, P, B, N, T, dt, init, alphas, x, u, K, d, active, ok, xt, ut, Jt, gw);
     // soft limits: the rollouts sum the cost terms, k_ilqr_soft_add the soft values (INIT: in the kernel)
     if (mu && init) { if (f32) { TMPC_FWD(true, float) } else { TMPC_FWD(true, double) } }
     else { if (f32) { TMPC_FWD(false, float) } else { TMPC_FWD(false, double) } }
@@ -1214,39 +1254,67 @@ struct LaunchIlqr {
   }
 };
 
-int launch_ilqr_backward(bool f32, hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, PList P, int B, int N,
-                         const double* x, const double* u, const double* rho, const int* active, const double* A,
-                         const double* Bm, const double* mu, const double* lam, double* jscratch, double* K,
-                         double* d, double* dV, int* ok) {
+// The tracking translation unit (tmpc_ilqr_trk.hip) defines TMPC_TRK_PART and builds the TRK instances behind the
+// *_trk launchers, which the fixed-goal unit's launchers hand a solve with a goal window to.
+#ifdef TMPC_TRK_PART
+#define TMPC_TRK_FN(name) name##_trk
+constexpr bool kTrkPart = true;
+#else
+#define TMPC_TRK_FN(name) name
+constexpr bool kTrkPart = false;
+#endif
+
+int TMPC_TRK_FN(launch_ilqr_backward)(bool f32, hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, PList P,
+                                      int B, int N, const double* x, const double* u, const double* rho,
+                                      const int* active, const double* A, const double* Bm, const double* mu,
+                                      const double* lam, double* jscratch, double* K, double* d, double* dV, int* ok,
+                                      const double* gw) {
+#ifndef TMPC_TRK_PART
+  if (gw)
+    return launch_ilqr_backward_trk(f32, s, nj, C, Cs, P, B, N, x, u, rho, active, A, Bm, mu, lam, jscratch, K, d, dV, ok,
+                                    gw);
+#endif
   return for_nj<1, NJMAX>(nj, [&](auto n) {
-    LaunchIlqrNJ<decltype(n)::value>::backward(f32, s, C, Cs, P, B, N, x, u, rho, active, A, Bm, mu, lam, jscratch, K, d,
-                                               dV, ok);
+    LaunchIlqrNJ<decltype(n)::value>::template backward<kTrkPart>(f32, s, C, Cs, P, B, N, x, u, rho, active, A, Bm, mu,
+                                                                  lam, jscratch, K, d, dV, ok, gw);
   });
 }
 
 // (Unlike tmpc_fd.hip / tmpc_kernels.hip, a runtime chain model keeps the CHAIN instance here: the rollout
 // measured 2.1 ms per launch on it against 3.2 ms on the general-topology one, arm6 B = 4096.)
-int launch_ilqr_forward(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, const CostDev* C,
-                        const ConstrDev* Cs, const double* mu, const double* lam, PList P, int B, int N, int T,
-                        double dt, int init, const double* alphas, const double* x, const double* u, const double* K,
-                        const double* d, const int* active, const int* ok, double* xt, double* ut, double* Jt) {
+int TMPC_TRK_FN(launch_ilqr_forward)(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M,
+                                     const CostDev* C, const ConstrDev* Cs, const double* mu, const double* lam,
+                                     PList P, int B, int N, int T, double dt, int init, const double* alphas,
+                                     const double* x, const double* u, const double* K, const double* d,
+                                     const int* active, const int* ok, double* xt, double* ut, double* Jt,
+                                     const double* gw) {
+#ifndef TMPC_TRK_PART
+  if (gw)
+    return launch_ilqr_forward_trk(f32, s, nj, chain, mid, M, C, Cs, mu, lam, P, B, N, T, dt, init, alphas, x, u, K, d,
+                                   active, ok, xt, ut, Jt, gw);
+#endif
   return dispatch_model(mid, nj, chain, [&](auto t) {
     using Tag = decltype(t);
-    LaunchIlqr<Tag::nj, Tag::chain, typename Tag::model>::forward(f32, s, M, C, Cs, mu, lam, P, B, N, T, dt, init, alphas,
-                                                                  x, u, K, d, active, ok, xt, ut, Jt);
+    LaunchIlqr<Tag::nj, Tag::chain, typename Tag::model>::template forward<kTrkPart>(
+        f32, s, M, C, Cs, mu, lam, P, B, N, T, dt, init, alphas, x, u, K, d, active, ok, xt, ut, Jt, gw);
   });
 }
 
-int launch_ilqr_init_cost(hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, const double* mu,
-                          const double* lam, PList P, int B, int N, const double* x, const double* u, const int* mask,
-                          double* Jt) {
+int TMPC_TRK_FN(launch_ilqr_init_cost)(hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, const double* mu,
+                                       const double* lam, PList P, int B, int N, const double* x, const double* u,
+                                       const int* mask, double* Jt, const double* gw) {
   if ((size_t)2 * N * sizeof(double) > 64 * 1024) return -1;
   if (nj > NJ_FULL && mu) return -2;   // a wide model: no soft limits
+#ifndef TMPC_TRK_PART
+  if (gw) return launch_ilqr_init_cost_trk(s, nj, C, Cs, mu, lam, P, B, N, x, u, mask, Jt, gw);
+#endif
   return for_nj<1, NJMAX>(nj, [&](auto n) {
-    LaunchIlqrNJ<decltype(n)::value>::init_cost(s, C, Cs, mu, lam, P, B, N, x, u, mask, Jt);
+    LaunchIlqrNJ<decltype(n)::value>::template init_cost<kTrkPart>(s, C, Cs, mu, lam, P, B, N, x, u, mask, Jt, gw);
   });
 }
+#undef TMPC_TRK_FN
 
+#ifndef TMPC_TRK_PART
 void launch_ilqr_decide(hipStream_t s, PList P, int B, int N, int NX, int NU, int T, int init, const double* alphas,
                         const SolverOpts& o, const double* Jt, const double* dV, const int* ok, const double* xt,
                         const double* ut, double* x, double* u, const ProbState& st, const TraceDev& tr,
@@ -1254,5 +1322,7 @@ void launch_ilqr_decide(hipStream_t s, PList P, int B, int N, int NX, int NU, in
   hipLaunchKernelGGL(k_ilqr_decide, dim3(B), dim3(64), 0, s, P, B, N, NX, NU, T, init, alphas, o, Jt, dV, ok, xt, ut, x,
                      u, st, tr, active_count, counters, activate);
 }
+
+#endif   // TMPC_TRK_PART
 
 }  // namespace tmpc

@@ -95,7 +95,20 @@ int launch_qp_grad(bool f32, hipStream_t s, int nj, bool chain, int mid, const M
 int launch_ls_terms(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, const CostDev* C, const ConstrDev* Cs,
                     const double* mu, const double* lam, PList P, int B, int N, int T, double dt, const double* alphas,
                     const double* x, const double* u, const double* xs, const double* dx, const double* du,
-                    const int* active, double* terms);
+                    const int* active, double* terms, const double* gw = nullptr);
+// The goal window (tmpc_set_reference): gw [B][N][nx], knot-major -- the state goal of problem b's knot k, which
+// the tracking instances of the goal-reading kernels (their TRK template argument) read in place of CostDev::xg.
+// A null gw launches the fixed-goal instances, which are the kernels as they were.  launch_goal_window resolves
+// the reference xref [R][nx][M] for one horizon solve: gw[b][k] = xref[(pbase + (pid ? pid[b] : b)) % R]
+// [:, min(k + step, M - 1)], for the problems in `mask` (null: all; a stream's slot with pid < 0 is skipped).
+void launch_goal_window(hipStream_t s, int B, int N, int nx, int R, int M, int step, const double* xref,
+                        const int* pid, int pbase, const int* mask, double* gw);
+// (the launchers of the tracking instances, which live in translation units of their own: tmpc_fd_trk.hip,
+// tmpc_ilqr_trk.hip; launch_ls_terms / launch_ilqr_* call them when gw is set)
+int launch_ls_terms_trk(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, const CostDev* C, const ConstrDev* Cs,
+                        const double* mu, const double* lam, PList P, int B, int N, int T, double dt, const double* alphas,
+                        const double* x, const double* u, const double* xs, const double* dx, const double* du,
+                        const int* active, double* terms, const double* gw);
 int launch_unit_fd(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, int K, double dt, const double* x,
                    const double* u, double* xnext, double* qdd);
 int launch_unit_minv(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, int K, const double* x, double* minv);
@@ -111,7 +124,7 @@ int launch_qp(hipStream_t s, int nj, const CostDev* C, PList P, int B, int N, do
               const double* x, const double* u,
               const int* active, const double* G, const double* A, const double* Bm, const double* cvec, double tol,
               int max_iter, int* iters, double* dx, double* du, double* lam, double* Sd, double* Sl, double* gam,
-              double* Pd, const double* jsoft, const double* guess, double* Sg);
+              double* Pd, const double* jsoft, const double* guess, double* Sg, const double* gw = nullptr);
 // largest Schur dimension N nx of the fused QP: up to 1024 rows S / P^-1 stay in registers, up to
 // QP_MAX_ROWS (the GM kernels: two rows per lane, 12 waves = 3 per SIMD, i.e. 168 VGPRs) in HBM
 // scratch Sg of qp_gm_doubles(B, N, nx) doubles.  1536 = arm6 at N = 128 (BASELINE config 5).
@@ -180,14 +193,27 @@ void launch_soft_outer(hipStream_t s, const ConstrDev* Cs, PList P, int B, int N
 int launch_ilqr_backward(bool f32, hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, PList P, int B, int N, const double* x,
                          const double* u, const double* rho, const int* active, const double* A, const double* Bm,
                          const double* mu, const double* lam, double* jscratch, double* K, double* d, double* dV,
-                         int* ok);
+                         int* ok, const double* gw = nullptr);
 int launch_ilqr_forward(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, const CostDev* C, const ConstrDev* Cs,
                         const double* mu, const double* lam, PList P, int B, int N, int T, double dt, int init,
                         const double* alphas, const double* x, const double* u, const double* K, const double* d,
-                        const int* active, const int* ok, double* xt, double* ut, double* Jt);
+                        const int* active, const int* ok, double* xt, double* ut, double* Jt,
+                        const double* gw = nullptr);
 int launch_ilqr_init_cost(hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, const double* mu,
                           const double* lam, PList P, int B, int N, const double* x, const double* u, const int* mask,
-                          double* Jt);
+                          double* Jt, const double* gw = nullptr);
+int launch_ilqr_backward_trk(bool f32, hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, PList P, int B, int N,
+                             const double* x, const double* u, const double* rho, const int* active, const double* A,
+                             const double* Bm, const double* mu, const double* lam, double* jscratch, double* K,
+                             double* d, double* dV, int* ok, const double* gw);
+int launch_ilqr_forward_trk(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, const CostDev* C,
+                            const ConstrDev* Cs, const double* mu, const double* lam, PList P, int B, int N, int T,
+                            double dt, int init, const double* alphas, const double* x, const double* u, const double* K,
+                            const double* d, const int* active, const int* ok, double* xt, double* ut, double* Jt,
+                            const double* gw);
+int launch_ilqr_init_cost_trk(hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, const double* mu,
+                              const double* lam, PList P, int B, int N, const double* x, const double* u,
+                              const int* mask, double* Jt, const double* gw);
 // counters: per-problem tallies [B][3] (problem-iterations, -, fresh gradients), summed by
 // launch_sum_counters; activate (init only, nullable): the real active flags -- st.active is then the
 // act_init mask, cleared as the problem enters its inner loop
@@ -233,6 +259,9 @@ constexpr int HARD_PCG_THREADS = 1024, HARD_PCG_MAX_SLOTS = 4;
 constexpr int HARD_PCG_MAX_ROWS = HARD_PCG_THREADS * HARD_PCG_MAX_SLOTS;
 constexpr int HARD_PCG_LDS_BYTES = 160 * 1024;   // all of a CU's LDS: vectors + preconditioner-block cache
 int launch_hard(hipStream_t s, int nj, const HardArgs& h);
+// the banded QP's cost gradient against the goal window gw (hard_grad's expressions with gw[b][k] for xg), into
+// gvec [B][N][nx+nu]: HardArgs.gvec of a tracking solve, so k_hard_schur / k_hard_dxu run unchanged
+int launch_hard_track_grad(hipStream_t s, int nj, const HardArgs& h, const double* gw, double* gvec);
 // dynamic LDS of k_hard_schur (one workgroup per problem): the cost gradient / piece record per knot
 // (3 nj doubles + 2 ints), the rows' piece knots (2 dmax ints, 16-byte rounded) and the shared Ghat
 // blocks (2 (2 nj)^2 + nj^2 doubles).  It grows with N: setup_hard refuses a horizon past the CU's LDS.

@@ -624,7 +624,9 @@ __device__ __forceinline__ double qp_schur_row(const CostDev* __restrict__ C, co
 //       QP_MODE_DXU   epilogue only, lambda read from lam_out (method S, after k_btsolve).
 //       GM: more than 1024 rows -- S and P^-1 rows in HBM (Sg, [B][4][NX/2][rows][2], PcgRowG), two rows
 //           per lane, LDS vectors of QP_MAX_ROWS rows.
-template <int NJ, int RPL, int MAXT, bool PK, int MODE, bool GM = false>
+//       TRK: the state goal of knot k from the goal window gw [B][N][NX] (tmpc_set_reference) in place of C->xg;
+//           the fixed-goal instances never touch gw.
+template <int NJ, int RPL, int MAXT, bool PK, int MODE, bool GM = false, bool TRK = false>
 __global__ void __launch_bounds__(MAXT) k_qp(const CostDev* __restrict__ C, PList P, int B, int N, double dt, int precond,
                                              const double* __restrict__ x, const double* __restrict__ u,
                                              const int* __restrict__ active, const double* __restrict__ Ginv,
@@ -635,7 +637,7 @@ __global__ void __launch_bounds__(MAXT) k_qp(const CostDev* __restrict__ C, PLis
                                              double* __restrict__ Sd_out, double* __restrict__ Sl_out,
                                              double* __restrict__ gam_out, double* __restrict__ Pd_out,
                                              const double* __restrict__ jsoft, const double* __restrict__ guess,
-                                             double* __restrict__ Sg) {
+                                             double* __restrict__ Sg, const double* __restrict__ gw) {
   constexpr int NX = 2 * NJ, NU = NJ;
   constexpr int VR = GM ? QP_MAX_ROWS : 1024;
   if (!P.has(blockIdx.x, B)) return;
@@ -662,8 +664,9 @@ __global__ void __launch_bounds__(MAXT) k_qp(const CostDev* __restrict__ C, PLis
     if (c < NX) {
       if (C->kind == COST_EE) { g_lds[e] = PK ? jsoft[(size_t)b * N * (NX + NU) + e] : 0.0; continue; }   // in jsoft
       const double* Qk = use_QF(C, kk, N) ? C->QF : C->Q;
+      const double* xg = TRK ? gw + ((size_t)b * N + kk) * NX : C->xg;
 #pragma unroll
-      for (int m = 0; m < NX; ++m) g += (S.x[m * N + kk] - C->xg[m]) * Qk[m * NX + c];
+      for (int m = 0; m < NX; ++m) g += (S.x[m * N + kk] - xg[m]) * Qk[m * NX + c];
     } else if (kk < K) {
 #pragma unroll
       for (int m = 0; m < NU; ++m) g += S.u[m * K + kk] * C->R[m * NU + (c - NX)];
@@ -1211,7 +1214,7 @@ struct LaunchNJ {
                  const double* u,
                  const int* active, const double* G, const double* A, const double* Bm, const double* cvec, double tol,
                  int max_iter, int* iters, double* dx, double* du, double* lam, double* Sd, double* Sl, double* gam,
-                 double* Pd, const double* jsoft, const double* guess, double* Sg) {
+                 double* Pd, const double* jsoft, const double* guess, double* Sg, const double* gw) {
     constexpr int NX = 2 * NJ;
     const int rows = N * NX;
     // S / P^-1 rows in HBM (Sg), two rows per lane, up to 1024 lanes (method S past 1024 rows runs the
@@ -1221,24 +1224,29 @@ struct LaunchNJ {
     const int threads = ((rows / rpl + 63) / 64) * 64;
     const size_t lds = qp_lds_doubles(N, NX, NJ, gm ? QP_MAX_ROWS : 1024) * sizeof(double);
 #define TMPC_QP_ARGS s, C, P, B, N, dt, precond, x, u, active, G, A, Bm, cvec, tol, max_iter, iters, dx, du, lam, Sd, \
-                     Sl, gam, Pd, jsoft, guess, Sg
-#define TMPC_QP_LAUNCH(PKV, MODEV)                                                                        \
+                     Sl, gam, Pd, jsoft, guess, Sg, gw
+#define TMPC_QP_LAUNCH_T(PKV, MODEV, TRKV)                                                                \
     if (gm)                                                                                                \
-      hipLaunchKernelGGL((k_qp<NJ, 2, QP_MAX_ROWS / 2, PKV, MODEV, true>), dim3(B), dim3(threads), lds, TMPC_QP_ARGS); \
+      hipLaunchKernelGGL((k_qp<NJ, 2, QP_MAX_ROWS / 2, PKV, MODEV, true, TRKV>), dim3(B), dim3(threads), lds, TMPC_QP_ARGS); \
     else if (rpl == 1)                                                                                     \
-      hipLaunchKernelGGL((k_qp<NJ, 1, 768, PKV, MODEV>), dim3(B), dim3(threads), lds, TMPC_QP_ARGS);        \
+      hipLaunchKernelGGL((k_qp<NJ, 1, 768, PKV, MODEV, false, TRKV>), dim3(B), dim3(threads), lds, TMPC_QP_ARGS); \
     else                                                                                                   \
-      hipLaunchKernelGGL((k_qp<NJ, 2, 512, PKV, MODEV>), dim3(B), dim3(threads), lds, TMPC_QP_ARGS);
+      hipLaunchKernelGGL((k_qp<NJ, 2, 512, PKV, MODEV, false, TRKV>), dim3(B), dim3(threads), lds, TMPC_QP_ARGS);
+    // a goal window (gw): the tracking instances
+#define TMPC_QP_LAUNCH(PKV, MODEV)                                                                        \
+    if (gw) { TMPC_QP_LAUNCH_T(PKV, MODEV, true) } else { TMPC_QP_LAUNCH_T(PKV, MODEV, false) }
     if constexpr (kWide<NJ>) {   // a wide model: registers / two rows per lane, no soft limits (launch_qp checks)
-#define TMPC_QP_LAUNCH_W(MODEV)                                                                            \
+#define TMPC_QP_LAUNCH_WT(MODEV, TRKV)                                                                     \
       if (rpl == 1)                                                                                        \
-        hipLaunchKernelGGL((k_qp<NJ, 1, 768, false, MODEV>), dim3(B), dim3(threads), lds, TMPC_QP_ARGS);    \
+        hipLaunchKernelGGL((k_qp<NJ, 1, 768, false, MODEV, false, TRKV>), dim3(B), dim3(threads), lds, TMPC_QP_ARGS); \
       else                                                                                                 \
-        hipLaunchKernelGGL((k_qp<NJ, 2, 512, false, MODEV>), dim3(B), dim3(threads), lds, TMPC_QP_ARGS);
+        hipLaunchKernelGGL((k_qp<NJ, 2, 512, false, MODEV, false, TRKV>), dim3(B), dim3(threads), lds, TMPC_QP_ARGS);
+#define TMPC_QP_LAUNCH_W(MODEV) if (gw) { TMPC_QP_LAUNCH_WT(MODEV, true) } else { TMPC_QP_LAUNCH_WT(MODEV, false) }
       if (mode == QP_MODE_PCG) { TMPC_QP_LAUNCH_W(QP_MODE_PCG) }
       else if (mode == QP_MODE_SCHUR) { TMPC_QP_LAUNCH_W(QP_MODE_SCHUR) }
       else { TMPC_QP_LAUNCH_W(QP_MODE_DXU) }
 #undef TMPC_QP_LAUNCH_W
+#undef TMPC_QP_LAUNCH_WT
     } else {
       // soft limits (jsoft != null): per-knot Ghat from HBM
       if (mode == QP_MODE_PCG) {
@@ -1250,6 +1258,7 @@ struct LaunchNJ {
       }
     }
 #undef TMPC_QP_LAUNCH
+#undef TMPC_QP_LAUNCH_T
 #undef TMPC_QP_ARGS
   }
   static void ginv_soft(hipStream_t s, const CostDev* C, const ConstrDev* Cs, PList P, int B, int N, const double* rho,
@@ -1271,6 +1280,9 @@ void for_each_qp(F&& set) {
     set(k_qp<NJ, 1, 768, PK, MD>);
     set(k_qp<NJ, 2, 512, PK, MD>);
     if constexpr (!kWide<NJ>) set(k_qp<NJ, 2, QP_MAX_ROWS / 2, PK, MD, true>);   // S / P^-1 rows in HBM
+    set(k_qp<NJ, 1, 768, PK, MD, false, true>);                                  // the tracking instances
+    set(k_qp<NJ, 2, 512, PK, MD, false, true>);
+    if constexpr (!kWide<NJ>) set(k_qp<NJ, 2, QP_MAX_ROWS / 2, PK, MD, true, true>);
     for_each_qp<NJ, PK, MD + 1>(set);
   }
 }
@@ -1699,6 +1711,33 @@ void launch_stream_init(hipStream_t s, int B, const StreamDev& sd, double* x, do
   hipLaunchKernelGGL(k_stream_init, dim3(B), dim3(256), 0, s, B, sd, x, u);
 }
 
+// ======================================================================= goal window (tmpc_internal.h)
+// One workgroup per problem resolves the reference xref [R][nx][M] (the layout of x) into the problem's rows of
+// the knot-major window gw [B][N][nx]: row (pbase + problem) % R, column min(k + step, M - 1).  Run once per
+// horizon solve (and for a stream's refilled slots), so the goal-reading kernels take one pointer and know
+// nothing of R, M or the step.  The stores are unit-stride; the reads stride by M, once.
+__global__ void __launch_bounds__(256) k_goal_window(int B, int N, int nx, int R, int M, int step,
+                                                     const double* __restrict__ xref, const int* __restrict__ pid,
+                                                     int pbase, const int* __restrict__ mask,
+                                                     double* __restrict__ gw) {
+  const int b = blockIdx.x;
+  if (b >= B || (mask && !mask[b])) return;
+  const int p = pid ? pid[b] : b;
+  if (p < 0) return;
+  const double* row = xref + (size_t)((pbase + p) % R) * nx * M;
+  double* out = gw + (size_t)b * N * nx;
+  for (int e = threadIdx.x; e < N * nx; e += blockDim.x) {
+    const int k = e / nx, m = e - k * nx;
+    const long long c = (long long)k + step;
+    out[e] = row[(size_t)m * M + (size_t)(c < M - 1 ? c : M - 1)];
+  }
+}
+
+void launch_goal_window(hipStream_t s, int B, int N, int nx, int R, int M, int step, const double* xref,
+                        const int* pid, int pbase, const int* mask, double* gw) {
+  hipLaunchKernelGGL(k_goal_window, dim3(B), dim3(256), 0, s, B, N, nx, R, M, step, xref, pid, pbase, mask, gw);
+}
+
 
 int launch_qp_minv(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, PList P, int B, int N,
                    const double* x, const int* need, double* minv) {
@@ -1737,7 +1776,7 @@ int launch_qp(hipStream_t s, int nj, const CostDev* C, PList P, int B, int N, do
               const double* x, const double* u,
               const int* active, const double* G, const double* A, const double* Bm, const double* cvec, double tol,
               int max_iter, int* iters, double* dx, double* du, double* lam, double* Sd, double* Sl, double* gam,
-              double* Pd, const double* jsoft, const double* guess, double* Sg) {
+              double* Pd, const double* jsoft, const double* guess, double* Sg, const double* gw) {
   const int rows = N * 2 * nj;
   if (rows > QP_MAX_ROWS) return -1;
   if (nj > NJ_FULL && (rows > 1024 || jsoft)) return -2;   // a wide model: no HBM-row instance, no soft limits
@@ -1746,7 +1785,7 @@ int launch_qp(hipStream_t s, int nj, const CostDev* C, PList P, int B, int N, do
   if (qp_lds_doubles(N, 2 * nj, nj, gm ? QP_MAX_ROWS : 1024) * sizeof(double) > 160 * 1024) return -3;
   return for_nj<1, NJMAX>(nj, [&](auto n) {
     LaunchNJ<decltype(n)::value>::qp(s, C, P, B, N, dt, precond, mode, x, u, active, G, A, Bm, cvec, tol, max_iter, iters,
-                                     dx, du, lam, Sd, Sl, gam, Pd, jsoft, guess, Sg);
+                                     dx, du, lam, Sd, Sl, gam, Pd, jsoft, guess, Sg, gw);
   });
 }
 int launch_ginv_soft(hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, PList P, int B, int N,

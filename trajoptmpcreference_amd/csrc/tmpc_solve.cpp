@@ -86,6 +86,12 @@ int run_qp(tmpc_ctx* ctx, int B, int N, double dt, int precond, const double* d_
     h.dx = w.dx; h.du = w.du; h.tol = ctx->opts.exit_tolerance_linSys; h.max_iter = ctx->opts.max_iter_linSys;
     h.iter = st.iter; h.Wtr = w.Wtr; h.tr_active = w.tr_active;
     HIP_OK(hipMemsetAsync(w.iters, 0, sizeof(int) * B, ctx->stream));
+    if (w.gw) {   // tracking: the cost gradient against the goal window, as the banded kernels' gvec input
+      BUF(double, hd_gvec, (size_t)B * N * 3 * nj);
+      Timed t(ctx, "hard_track_grad");
+      LAUNCH_OK(launch_hard_track_grad(ctx->stream, nj, h, w.gw, hd_gvec));
+      h.gvec = hd_gvec;
+    }
     return run_hard_qp(ctx, nj, h);
   }
   if (precond == 0) {   // method S: Schur blocks -> direct solve -> dxu
@@ -93,7 +99,7 @@ int run_qp(tmpc_ctx* ctx, int B, int N, double dt, int precond, const double* d_
       Timed t(ctx, "schur");
       LAUNCH_OK(launch_qp(ctx->stream, nj, ctx->dcost, P, nb, N, dt, PRECOND_SS, QP_MODE_SCHUR, d_x, d_u, st.active, G,
                           w.A, w.Bm, w.cvec, 0.0, 0, w.iters, w.dx, w.du, nullptr, w.Sd, w.Sl, w.gam, nullptr,
-                          w.jsoft, nullptr, nullptr));
+                          w.jsoft, nullptr, nullptr, w.gw));
     }
     {
       Timed t(ctx, "btsolve");
@@ -103,7 +109,7 @@ int run_qp(tmpc_ctx* ctx, int B, int N, double dt, int precond, const double* d_
       Timed t(ctx, "dxu");
       LAUNCH_OK(launch_qp(ctx->stream, nj, ctx->dcost, P, nb, N, dt, PRECOND_SS, QP_MODE_DXU, d_x, d_u, st.active, G, w.A,
                           w.Bm, w.cvec, 0.0, 0, w.iters, w.dx, w.du, w.lam, nullptr, nullptr, nullptr, nullptr,
-                          w.jsoft, nullptr, nullptr));
+                          w.jsoft, nullptr, nullptr, w.gw));
     }
     return 0;
   }
@@ -113,7 +119,7 @@ int run_qp(tmpc_ctx* ctx, int B, int N, double dt, int precond, const double* d_
                         w.Bm, w.cvec, ctx->opts.exit_tolerance_linSys, ctx->opts.max_iter_linSys, w.iters, w.dx,
                         w.du, keep_blocks ? w.lam : w.lam_keep, keep_blocks ? w.Sd : nullptr,
                         keep_blocks ? w.Sl : nullptr, keep_blocks ? w.gam : nullptr, keep_blocks ? w.Pd : nullptr,
-                        w.jsoft, w.guess, w.Sg));
+                        w.jsoft, w.guess, w.Sg, w.gw));
   }
   return 0;
 }
@@ -153,6 +159,24 @@ int alloc_work(tmpc_ctx* ctx, int B, int N, Work& w, bool with_blocks) {
     w.U = btU;
     w.Y = btY;
   }
+  return 0;
+}
+
+int goal_window(tmpc_ctx* ctx, int B, int N, int rows, const char* rows_name, const int* pid, int pbase,
+                const int* mask, double** gw) {
+  *gw = nullptr;
+  if (!ctx->ref_R) return 0;
+  if (ctx->hcost.kind == COST_EE)
+    return fail(ctx, "a state reference (tmpc_set_reference) with UrdfCost: the task-space goal stays constant; "
+                "clear the reference (tmpc_set_reference with R = 0)");
+  if (ctx->ref_R != 1 && ctx->ref_R != rows)
+    return fail(ctx, "reference rows R = %d: must be 1 or the %s (%d)", ctx->ref_R, rows_name, rows);
+  const int nx = 2 * ctx->hmodel.n;
+  BUF(double, goal_win, (size_t)B * N * nx);
+  launch_goal_window(ctx->stream, B, N, nx, ctx->ref_R, ctx->ref_M, ctx->ref_step, ctx->ref_dev, pid, pbase, mask,
+                     goal_win);
+  HIP_OK(hipGetLastError());
+  *gw = goal_win;
   return 0;
 }
 
@@ -501,6 +525,11 @@ static int outer_run(tmpc_ctx* ctx, int B, int N, Outer& o, double* d_x, double*
                           op.max_iter_softConstraints, d_x, d_u, o.smu, o.slam, o.sphi, o.outer_active, o.outer_iter,
                           o.exit_soft, ac + 1, &o.st, act_init, op.rho_init_SQP_DDP, sd, o.w.xs, &o.tr, lam_keep);
         HIP_OK(hipGetLastError());
+        if (sd && o.w.gw) {   // tracking: the goals of the problems that just entered a slot (act_init)
+          launch_goal_window(ctx->stream, B, N, nx, ctx->ref_R, ctx->ref_M, 0, ctx->ref_dev, sd->slot_pid, sd->pbase,
+                             act_init, o.w.gw);
+          HIP_OK(hipGetLastError());
+        }
       }
       // restarted passes (act_init, set by k_soft_outer) and a stream's new problems: initial cost / merit, then
       // into the inner loop; masked by act_init, so a no-op when no pass restarted
@@ -595,12 +624,17 @@ int sqp_device(tmpc_ctx* ctx, int B, int N, double dt, int linsys, double* d_x, 
     launch_stream_init(ctx->stream, B, *sd, d_x, d_u);
     HIP_OK(hipGetLastError());
   }
+  // the goals of a tracking solve (a stream: of the problems now in the slots)
+  if ((rc = goal_window(ctx, B, N, sd ? sd->period : B, sd ? "stream's period" : "batch size",
+                        sd ? sd->slot_pid : nullptr, sd ? sd->pbase : 0, nullptr, &w.gw)))
+    return rc;
   // initial J, c, merit (:541-548)
   auto init_merit = [&](int* mask, int* ac, int* activate) -> int {
     ProbState sti = st;
     sti.active = mask;
     LAUNCH_OK(launch_ls_terms(val32(ctx), ctx->stream, nj, chain, ctx->model_id, ctx->dmodel, ctx->dcost, ctx->dlim, L.smu, L.slam,
-                              alv.P, alv.nb, N, 1, dt, alphas + T, d_x, d_u, w.xs, nullptr, nullptr, mask, terms));
+                              alv.P, alv.nb, N, 1, dt, alphas + T, d_x, d_u, w.xs, nullptr, nullptr, mask, terms,
+                              w.gw));
     if (hterms) LAUNCH_OK(hard_ls(ctx, nj, hard, B, N, 1, alphas + T, d_x, d_u, nullptr, nullptr, mask));
     launch_ls_decide(ctx->stream, alv.P, alv.nb, N, nx, nj, 1, LS_MODE_INIT, soft, alphas + T, so, terms, d_x, d_u, w.dx, w.du,
                      sti, nullptr, L.tr, ac, nullptr, hterms, nullptr, activate);
@@ -614,7 +648,7 @@ int sqp_device(tmpc_ctx* ctx, int B, int N, double dt, int linsys, double* d_x, 
     {
       Timed t(ctx, "ls_terms");
       LAUNCH_OK(launch_ls_terms(val32(ctx), ctx->stream, nj, chain, ctx->model_id, ctx->dmodel, ctx->dcost, ctx->dlim, L.smu, L.slam,
-                                alv.P, alv.nb, N, T, dt, alphas, d_x, d_u, w.xs, w.dx, w.du, st.active, terms));
+                                alv.P, alv.nb, N, T, dt, alphas, d_x, d_u, w.xs, w.dx, w.du, st.active, terms, w.gw));
       if (hterms) LAUNCH_OK(hard_ls(ctx, nj, hard, B, N, T, alphas, d_x, d_u, w.dx, w.du, st.active));
     }
     Timed t(ctx, "ls_decide");
@@ -669,13 +703,13 @@ int ilqr_sweeps(tmpc_ctx* ctx, int N, double dt, const double* d_x, const double
   {
     Timed t(ctx, "ilqr_backward");
     LAUNCH_OK(launch_ilqr_backward(ric32(ctx), ctx->stream, nj, ctx->dcost, ctx->dlim, P, nb, N, d_x, d_u, st.rho,
-                                   st.active, w.A, w.Bm, q.smu, q.slam, q.jac, q.K, q.d, q.dV, q.ok));
+                                   st.active, w.A, w.Bm, q.smu, q.slam, q.jac, q.K, q.d, q.dV, q.ok, w.gw));
   }
   {
     Timed t(ctx, "ilqr_forward");
     LAUNCH_OK(launch_ilqr_forward(val32(ctx), ctx->stream, nj, chain, ctx->model_id, ctx->dmodel, ctx->dcost, ctx->dlim,
                                   q.smu, q.slam, P, nb, N, q.T, dt, 0, q.alphas, d_x, d_u, q.K, q.d, st.active, q.ok,
-                                  q.xt, q.ut, q.J));
+                                  q.xt, q.ut, q.J, w.gw));
   }
   return 0;
 }
@@ -692,7 +726,7 @@ int ilqr_device(tmpc_ctx* ctx, int B, int N, double dt, double* d_x, double* d_u
   const int T = q.T;
   Outer L{};
   if ((rc = outer_alloc(ctx, B, N, false, sd != nullptr, L))) return rc;
-  const Work& w = L.w;
+  Work& w = L.w;
   const ProbState& st = L.st;
   const AliveList& alv = L.alv;
   BUF(unsigned long long, il_prob_counters, (size_t)B * 3);   // per-problem tallies of k_ilqr_decide
@@ -719,12 +753,16 @@ int ilqr_device(tmpc_ctx* ctx, int B, int N, double dt, double* d_x, double* d_u
     // iLQR iterates are rollouts: start from the rollout of u from x[:, 0]
     LAUNCH_OK(launch_rollout(val32(ctx), ctx->stream, nj, chain, ctx->model_id, ctx->dmodel, B, N, dt, d_x, d_u));
   }
+  // the goals of a tracking solve (a stream: of the problems now in the slots)
+  if ((rc = goal_window(ctx, B, N, sd ? sd->period : B, sd ? "stream's period" : "batch size",
+                        sd ? sd->slot_pid : nullptr, sd ? sd->pbase : 0, nullptr, &w.gw)))
+    return rc;
   // J at the current trajectory
   auto init_cost = [&](int* mask, int* ac, int* activate) -> int {
     ProbState sti = st;
     sti.active = mask;
     LAUNCH_OK(launch_ilqr_init_cost(ctx->stream, nj, ctx->dcost, ctx->dlim, L.smu, L.slam, alv.P, alv.nb, N, d_x, d_u,
-                                    mask, q.J));
+                                    mask, q.J, w.gw));
     launch_ilqr_decide(ctx->stream, alv.P, alv.nb, N, nx, nj, 1, 1, q.alphas, so, q.J, q.dV, q.ok, q.xt, q.ut, d_x, d_u,
                        sti, L.tr, ac, nullptr, activate);
     HIP_OK(hipGetLastError());
@@ -799,6 +837,11 @@ int stream_solve(tmpc_ctx* ctx, int N, double dt, int linsys, const tmpc_stream*
   int rc = linsys < 0 ? check_ready(ctx, 1, N, false) : check_ready(ctx, 1, N);
   if (rc) return rc;
   if (!s) return fail(ctx, "null stream");
+  if (ctx->ref_R && ctx->hcost.kind == COST_EE)
+    return fail(ctx, "a state reference (tmpc_set_reference) with UrdfCost: the task-space goal stays constant; "
+                "clear the reference (tmpc_set_reference with R = 0)");
+  if (ctx->ref_R > 1 && ctx->ref_R != s->period)
+    return fail(ctx, "reference rows R = %d: must be 1 or the stream's period (%d)", ctx->ref_R, s->period);
   hipSetDevice(ctx->device);
   const int K = std::max(1, std::min({s->substreams, s->slots, std::max(1, s->problems), 8}));
   if (K == 1 || s->substreams <= 1) return stream_one(ctx, N, dt, linsys, s, 0);
@@ -818,6 +861,10 @@ int stream_solve(tmpc_ctx* ctx, int N, double dt, int linsys, const tmpc_stream*
     sub->opts = ctx->opts;
     sub->has_model = ctx->has_model;
     sub->has_cost = ctx->has_cost;
+    sub->ref_dev = ctx->ref_dev;   // borrowed: read-only, and this call outlives the sub-streams' solves
+    sub->ref_R = ctx->ref_R;
+    sub->ref_M = ctx->ref_M;
+    sub->ref_step = 0;
     sub->soft_B = sub->soft_N = -1;
     sub->stats.clear();
     sub->kbytes.clear();
@@ -883,8 +930,10 @@ int mpc_device(tmpc_ctx* ctx, int B, int N, double dt, int solver, int steps, do
   HIP_OK(hipMemcpy2DAsync(d_xe, (size_t)(steps + 1) * sizeof(double), d_x, (size_t)N * sizeof(double), sizeof(double),
                           (size_t)B * nx, hipMemcpyDeviceToDevice, ctx->stream));
   for (int s = 0; s < steps; ++s) {
+    ctx->ref_step = s;   // a reference slides one column per step (goal_window)
     rc = ilqr ? ilqr_device(ctx, B, N, dt, d_x, d_u, nullptr)
               : sqp_device(ctx, B, N, dt, solver, d_x, d_u, nullptr, /*keep_warm=*/s > 0);
+    ctx->ref_step = 0;
     if (rc) return rc;
     for (int i = 0; i < 3; ++i) sum_counters[i] += ctx->last_counters[i];
     if (!ilqr && ctx->opts.pcg_warm_start && precond_of(solver) != 0 && !qp_banded(ctx, N)) {

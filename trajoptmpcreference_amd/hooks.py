@@ -25,7 +25,7 @@ import copy
 import numpy as np
 
 from .constraint import TrajoptConstraint
-from .cost import QuadraticCost, TrajoptCost, UrdfCost
+from .cost import QuadraticCost, TrackingCost, TrajoptCost, UrdfCost
 from .plant import TrajoptPlant, URDFPlant
 
 COST_HOOKS = ("value", "gradient", "hessian", "get_currQ", "delta_x", "jacobian_tot_state", "compute_J", "_kin")
@@ -45,11 +45,11 @@ def overrides(obj, base, names):
 
 
 def device_cost(cost):
-    """The cost the device evaluates, or None when its hooks are the caller's: QuadraticCost / UrdfCost
-    themselves, or a subclass that overrides none of their hooks."""
+    """The cost the device evaluates, or None when its hooks are the caller's: QuadraticCost / TrackingCost /
+    UrdfCost themselves, or a subclass that overrides none of their hooks."""
     if not isinstance(cost, QuadraticCost):
         return None
-    base = UrdfCost if isinstance(cost, UrdfCost) else QuadraticCost
+    base = UrdfCost if isinstance(cost, UrdfCost) else TrackingCost if isinstance(cost, TrackingCost) else QuadraticCost
     return None if overrides(cost, base, COST_HOOKS) else cost
 
 

@@ -15,7 +15,7 @@ import numpy as np
 from . import _native, hooks
 from ._options import NO_OPTIONS, fresh
 from .constraint import TrajoptConstraint
-from .cost import QuadraticCost, TrajoptCost, UrdfCost
+from .cost import QuadraticCost, TrackingCost, TrajoptCost, UrdfCost
 from .plant import TrajoptPlant, URDFPlant
 
 
@@ -143,7 +143,23 @@ class TrajoptMPCReference:
         ctx.set_options(**{v: options[k] for k, v in _OPTION_MAP.items()})
         return ctx
 
-    def _context(self, options):
+    def _reference(self, goal, x):
+        """A `goal=` argument ([B][nx] per-problem goals or [B][nx][M] per-knot references, B the batch size
+        of x) as the device's reference array [R][nx][M], or None.  Checked before any device work."""
+        if goal is None:
+            return None
+        if isinstance(self.cost, UrdfCost):
+            raise NotImplementedError("goal= with UrdfCost: the task-space goal stays constant (QuadraticCost / "
+                                      "TrackingCost take per-problem goals)")
+        if self._hooks():
+            raise NotImplementedError("goal= runs on the device plugins; a plugin-hook cost sets its own goal")
+        return _native.reference_array(goal, np.shape(x)[0], self._dims()[0])
+
+    def _context(self, options, xref=None):
+        """The plant's context configured for this solver.  xref: the call's reference [R][nx][M] (goal=); else a
+        TrackingCost's from its current shift on; else none.  It is set or cleared on every call, and the solver's
+        methods clear it again after their solve: the context is shared per device, and a reference left behind
+        would steer the next solve."""
         if self._hooks():
             which = [name for name, ok in (("cost", hooks.device_cost(self.cost) is not None),
                                            ("plant", hooks.device_plant(self.plant)),
@@ -174,23 +190,29 @@ class TrajoptMPCReference:
         ctx.set_options(**{v: options[k] for k, v in _OPTION_MAP.items()},
                         pcg_warm_start=int(bool(options.get("pcg_warm_start", False))), precision=_PRECISION[prec])
         ctx.set_box_limits(spec)
+        if xref is None and isinstance(c, TrackingCost):
+            xref = c.window()[None]
+        ctx.set_reference(xref)
         return ctx
 
     def SQP_batch(self, x, u, N: int, dt: float, LINEAR_SYSTEM_SOLVER_METHOD=SQPSolverMethods.PCG_SS, options=None,
-                  soft_state=None, hard_active=False):
+                  soft_state=None, hard_active=False, goal=None):
         """B problems at once: x [B][nx][N], u [B][nu][N-1] -> dict of per-problem results.
         With soft limits every problem starts from the constraint objects' mu / lambda / phi
         (or from soft_state = (mu, lam, phi), each [B][N][6n]); the final per-problem
         constants are returned as r["soft_state"].  hard_active: with hard limits, also every QP's
-        active set (r["trace"]["hard_active"] [B][max_iter+1][N] bitmasks, include/tmpc.h)."""
+        active set (r["trace"]["hard_active"] [B][max_iter+1][N] bitmasks, include/tmpc.h).
+        goal: per-problem goals [B][nx] or per-knot references [B][nx][M] (knot k tracks column min(k, M - 1);
+        one row serves every problem) in place of the cost object's goal, for this call."""
         options = {} if options is None else options
         self.set_default_options(options)
+        xref = self._reference(goal, x)
         # method N (solveKKTSystem, the dense KKT solve, :313-359) has the Schur complement's solution and
         # runs the direct Schur path with the same least-squares fallback (include/tmpc.h TMPC_LINSYS_N)
         method = _method_name(LINEAR_SYSTEM_SOLVER_METHOD)
         if self._hooks():
             return self._sqp_hooks_batch(x, u, N, dt, method, options, soft_state)
-        ctx = self._context(options)
+        ctx = self._context(options, xref)
         x = np.asarray(x, dtype=np.float64)
         u = np.asarray(u, dtype=np.float64)
         self._check_xu(x, u, N)
@@ -203,7 +225,10 @@ class TrajoptMPCReference:
             if soft_state is None:
                 soft_state = [np.broadcast_to(a, (B,) + a.shape) for a in self.other_constraints.pack_state(N)]
             ctx.set_soft_state(B, N, *soft_state)
-        r = ctx.sqp_solve_batch(x, u, N, dt, method, hard_active=hard_active)
+        try:
+            r = ctx.sqp_solve_batch(x, u, N, dt, method, hard_active=hard_active)
+        finally:
+            ctx.set_reference(None)   # the context is shared per device: the reference ends with the call
         if soft:
             r["soft_state"] = ctx.get_soft_state(B, N)
         return r
@@ -291,14 +316,14 @@ class TrajoptMPCReference:
         return (r["x"][0], r["u"][0], self.exit_sqp, self.exit_soft, int(r["outer_iter"][0]), it)
 
     # ------------------------------------------------------------------ iLQR (MPCSolverMethods.iLQR)
-    def iLQR_batch(self, x, u, N: int, dt: float, options=None, soft_state=None):
+    def iLQR_batch(self, x, u, N: int, dt: float, options=None, soft_state=None, goal=None):
         """Batched iLQR (algorithm in oracle/ilqr.py -- the reference defines only
         the MPCSolverMethods.iLQR enum value).  Same plugins, *_SQP_DDP options, rho schedule, exit
         codes and soft-constraint outer loop as SQP_batch; x is replaced by the rollout of u from
-        x[:, :, 0]."""
+        x[:, :, 0].  goal: as SQP_batch's."""
         options = {} if options is None else options
         self.set_default_options(options)
-        ctx = self._context(options)
+        ctx = self._context(options, self._reference(goal, x))
         x = np.asarray(x, dtype=np.float64)
         u = np.asarray(u, dtype=np.float64)
         self._check_xu(x, u, N)
@@ -308,7 +333,10 @@ class TrajoptMPCReference:
             if soft_state is None:
                 soft_state = [np.broadcast_to(a, (B,) + a.shape) for a in self.other_constraints.pack_state(N)]
             ctx.set_soft_state(B, N, *soft_state)
-        r = ctx.ilqr_solve_batch(x, u, N, dt)
+        try:
+            r = ctx.ilqr_solve_batch(x, u, N, dt)
+        finally:
+            ctx.set_reference(None)
         if soft:
             r["soft_state"] = ctx.get_soft_state(B, N)
         return r
@@ -343,13 +371,17 @@ class TrajoptMPCReference:
 
     # ------------------------------------------------------------------ receding-horizon MPC
     def MPC_batch(self, x, u, N: int, dt: float, SOLVER_METHOD=MPCSolverMethods.QP_PCG_SS, options=None,
-                  mpc_steps: int = 1, soft_state=None):
+                  mpc_steps: int = 1, soft_state=None, goal=None):
         """Receding-horizon loop for B problems (algorithm in oracle/mpc.py -- the
         reference calls runMPCExample but never defines it, F1).  Each step solves the horizon with
         SQP (QP-S / QP-PCG-*) or iLQR warm-started from the shifted previous solution, applies u[:, 0]
         for one Euler step and shifts; the cost's QF_start and the soft-limit constants shift as the
         reference's hooks do (TrajoptCost.py:100-104, TrajoptConstraint.py:168-176).  Returns the
-        executed states [B][nx][steps+1] / controls [B][nu][steps] and per-step exit codes / iterations."""
+        executed states [B][nx][steps+1] / controls [B][nu][steps] and per-step exit codes / iterations.
+        goal: as SQP_batch's; knot k of step s tracks column min(k + s, M - 1), so a reference slides one
+        column per step and holds its last column once it runs out.  A TrackingCost's shift advances by
+        mpc_steps (shift_reference), as QF_start moves -- unless goal= replaced its reference for this call: the
+        loop then never tracked the cost's own reference, and its shift stays."""
         options = {} if options is None else options
         self.set_default_options(options)
         m = SOLVER_METHOD.value if isinstance(SOLVER_METHOD, MPCSolverMethods) else str(SOLVER_METHOD)
@@ -359,7 +391,7 @@ class TrajoptMPCReference:
             solver = m[3:]   # QP-N: the dense KKT solve, the Schur complement's solution (method N of SQP)
         else:
             raise NotImplementedError(f"MPC solver {m}: use iLQR, QP-N, QP-S, QP-PCG-J, QP-PCG-BJ or QP-PCG-SS")
-        ctx = self._context(options)
+        ctx = self._context(options, self._reference(goal, x))
         x = np.asarray(x, dtype=np.float64)
         u = np.asarray(u, dtype=np.float64)
         self._check_xu(x, u, N)
@@ -369,11 +401,16 @@ class TrajoptMPCReference:
             if soft_state is None:
                 soft_state = [np.broadcast_to(a, (B,) + a.shape) for a in self.other_constraints.pack_state(N)]
             ctx.set_soft_state(B, N, *soft_state)
-        r = ctx.mpc_batch(x, u, N, dt, solver, int(mpc_steps))
+        try:
+            r = ctx.mpc_batch(x, u, N, dt, solver, int(mpc_steps))
+        finally:
+            ctx.set_reference(None)
         if soft:
             r["soft_state"] = ctx.get_soft_state(B, N)
         if self.cost.QF_start is not None:
             self.cost.QF_start = max(self.cost.QF_start - int(mpc_steps), 0)
+        if goal is None and isinstance(self.cost, TrackingCost):
+            self.cost.shift_reference(int(mpc_steps))
         return r
 
     def MPC(self, x, u, N: int, dt: float, SOLVER_METHOD=MPCSolverMethods.QP_PCG_SS, options=None, mpc_steps: int = 1):
@@ -554,7 +591,10 @@ class TrajoptMPCReference:
         con = self.other_constraints
         if any(c.is_soft_constraint_mode() for _, c in con.limits()):   # the objects' current mu / lambda
             ctx.set_soft_state(1, N, *[a[None] for a in con.pack_state(N)])
-        r = ctx.qp_batch(x[None], u[None], N, dt, rho, method, want_blocks=False, guess=guess, xs=xs)
+        try:
+            r = ctx.qp_batch(x[None], u[None], N, dt, rho, method, want_blocks=False, guess=guess, xs=xs)
+        finally:
+            ctx.set_reference(None)
         self.n_inner_iter = int(r["pcg_iters"][0])
         dxul = r["dxul"][0]
         if not any(c.is_hard_constraint_mode() for _, c in con.limits()):
