@@ -37,9 +37,9 @@
 extern "C" {
 #endif
 
-#define TMPC_ABI_VERSION 11  /* 11: tmpc_ilqr_step_batch (later added, same version: tmpc_set_reference,
-                                tmpc_set_reference_device); 10: tmpc_*_solve_stream_device; 9: tmpc_pcg_dense_batch;
-                                8: tmpc_qp_blocks_batch */
+#define TMPC_ABI_VERSION 12  /* 12: tmpc_qp_last_inputs; 11: tmpc_ilqr_step_batch (later added, same version:
+                                tmpc_set_reference, tmpc_set_reference_device); 10: tmpc_*_solve_stream_device;
+                                9: tmpc_pcg_dense_batch; 8: tmpc_qp_blocks_batch */
 
 /* SQPSolverMethods (TrajoptMPCReference.py:13-18). */
 #define TMPC_LINSYS_S 1      /* Schur complement, direct block-tridiagonal solve (:441-446; np.linalg.solve in the reference) */
@@ -340,6 +340,21 @@ int tmpc_fd_grad_batch(tmpc_ctx* ctx, int K, double dt, const double* x, const d
 int tmpc_qp_batch(tmpc_ctx* ctx, int B, int N, double dt, int linsys, const double* rho, const double* x,
                   const double* u, const double* xs, const double* guess, double* dxul, int32_t* pcg_iters,
                   double* S_diag, double* S_lo, double* gamma, double* P_diag);
+
+/* What the QP of the last tmpc_qp_batch call consumed (ABI 12; same B, N; the fused path: no hard box limits and
+ * N nx within the fused kernel's rows), read back from the context's buffers -- nothing is recomputed.  Host
+ * arrays, each nullable:
+ *   A [B][N-1][nx][nx], Bm [B][N-1][nx][nu]   the integrator Jacobians (k_qp_grad's output);
+ *   c [B][N][nx]                              the defects, c_0 = x_0 - xs (k_qp_fd's output);
+ *   Ghat_x [B][N][nx][nx], Ghat_u [B][N-1][nu][nu]   (G_k + rho I)^-1 per knot, its state and control blocks:
+ *                                             without soft limits the three inverses of Q, QF and R + rho I
+ *                                             (k_ginv) expanded per knot, QF at the terminal knot and from
+ *                                             QF_start on; with soft limits k_ginv_soft's per-knot blocks.
+ * With these a reference can form S, gamma and dxu from exactly the kernel's inputs.  Fails when there was no
+ * such call (or a later solve or tmpc_ilqr_step_batch reused the buffers), when B or N differ, or when that call
+ * took the banded path (tmpc_qp_hard_info has its detail). */
+int tmpc_qp_last_inputs(tmpc_ctx* ctx, int B, int N, double* A, double* Bm, double* c, double* Ghat_x,
+                        double* Ghat_u);
 
 /* One iLQR iteration's sweeps for B problems (ABI 11; algorithm: oracle/ilqr.py), without the decision: what
  * an iteration of tmpc_ilqr_solve_batch runs before its acceptance test -- the integrator Jacobians, the

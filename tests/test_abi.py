@@ -53,7 +53,8 @@ def test_binding_matches_header():
     from trajoptmpcreference_amd import _native
     assert sorted(_native.SIGNATURES) == header_functions()
     lib = _native.load_library()
-    assert lib.tmpc_abi_version() == 11
+    assert lib.tmpc_abi_version() == 12
+    assert "tmpc_qp_last_inputs" in _native.SIGNATURES   # ABI 12
 
 
 def test_options_struct_layout_and_defaults():
@@ -86,6 +87,12 @@ def test_null_context_is_an_error_not_a_crash():
     lib = _native.load_library()
     assert lib.tmpc_set_options(None, None) < 0
     assert lib.tmpc_last_error(None) == b"null context"
+
+
+def test_qp_last_inputs_null_context_is_an_error():
+    from trajoptmpcreference_amd import _native
+    lib = _native.load_library()
+    assert lib.tmpc_qp_last_inputs(None, 1, 2, None, None, None, None, None) < 0
 
 
 def test_trace_struct_layout():

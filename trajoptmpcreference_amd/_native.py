@@ -114,6 +114,7 @@ SIGNATURES = {
     "tmpc_fd_grad_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     "tmpc_qp_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip,
                                 _dp, _dp, _dp, _dp]),
+    "tmpc_qp_last_inputs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "tmpc_ilqr_step_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp,
                                        _dp, _dp, _ip, _dp, _dp, _dp, _dp]),
     "tmpc_qp_blocks_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp,
@@ -471,6 +472,18 @@ class Context:
                                            _ptr(Pd)),
                     "tmpc_qp_batch")
         return dict(dxul=dxul, pcg_iters=iters, S_diag=Sd, S_lo=Sl, gamma=g, P_diag=Pd)
+
+    def qp_last_inputs(self, B, N):
+        """What the QP of the last qp_batch (same B, N; the fused path) consumed (tmpc_qp_last_inputs): dict(A
+        [B][N-1][nx][nx], Bm [B][N-1][nx][nu], c [B][N][nx], Ghat_x [B][N][nx][nx], Ghat_u [B][N-1][nu][nu])."""
+        n = self.model.n
+        nx, K = 2 * n, int(N) - 1
+        out = dict(A=np.zeros((B, K, nx, nx)), Bm=np.zeros((B, K, nx, n)), c=np.zeros((B, N, nx)),
+                   Ghat_x=np.zeros((B, N, nx, nx)), Ghat_u=np.zeros((B, K, n, n)))
+        self._check(self.lib.tmpc_qp_last_inputs(self.h, int(B), int(N), _ptr(out["A"]), _ptr(out["Bm"]),
+                                                 _ptr(out["c"]), _ptr(out["Ghat_x"]), _ptr(out["Ghat_u"])),
+                    "tmpc_qp_last_inputs")
+        return out
 
     def alpha_count(self):
         """T, the line-search trials of the options: 1, f, f^2, ... while the previous entry is > alpha_min

@@ -215,6 +215,7 @@ int tmpc_qp_batch(tmpc_ctx* ctx, int B, int N, double dt, int linsys, const doub
     HIP_OK(hipMemcpy(w.lam, lr.data(), lr.size() * sizeof(double), hipMemcpyHostToDevice));
   }
   resolve_timings(ctx);
+  ctx->qp_last = {B, N, nj, ctx->hcost.QF_start, w.jsoft != nullptr, banded};   // tmpc_qp_last_inputs
   if (dxul) {
     std::vector<double> lam((size_t)B * N * nx);
     HIP_OK(hipMemcpy(lam.data(), w.lam, lam.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -226,6 +227,55 @@ int tmpc_qp_batch(tmpc_ctx* ctx, int B, int N, double dt, int linsys, const doub
   if (gamma) HIP_OK(hipMemcpy(gamma, w.gam, sizeof(double) * B * N * nx, hipMemcpyDeviceToHost));
   if (P_diag && precond != PRECOND_J && precond != 0)
     HIP_OK(hipMemcpy(P_diag, w.Pd, sizeof(double) * B * N * nx * nx, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int tmpc_qp_last_inputs(tmpc_ctx* ctx, int B, int N, double* A, double* Bm, double* c, double* Ghat_x,
+                        double* Ghat_u) {
+  if (!ctx) return -1;
+  const auto& ql = ctx->qp_last;
+  if (ql.B == 0)
+    return fail(ctx, "tmpc_qp_last_inputs: no tmpc_qp_batch call to report (none yet, or a later call reused its "
+                "buffers)");
+  if (ql.B != B || ql.N != N)
+    return fail(ctx, "tmpc_qp_last_inputs: the last tmpc_qp_batch was B=%d N=%d, asked for B=%d N=%d", ql.B, ql.N, B, N);
+  if (ql.banded)
+    return fail(ctx, "tmpc_qp_last_inputs: the last tmpc_qp_batch took the banded path (hard box limits, or N * nx "
+                "past %d rows); tmpc_qp_hard_info has its detail", QP_MAX_ROWS);
+  hipSetDevice(ctx->device);
+  const int nj = ql.nj, nx = 2 * nj, K = N - 1;
+  // the named buffers of that call (alloc_work, init_soft): the same sizes, so nothing is reallocated
+  BUF(double, cvec, (size_t)B * N * nx);
+  BUF(double, Amat, (size_t)B * K * nx * nx);
+  BUF(double, Bmat, (size_t)B * K * nx * nj);
+  if (A) HIP_OK(hipMemcpy(A, Amat, sizeof(double) * B * K * nx * nx, hipMemcpyDeviceToHost));
+  if (Bm) HIP_OK(hipMemcpy(Bm, Bmat, sizeof(double) * B * K * nx * nj, hipMemcpyDeviceToHost));
+  if (c) HIP_OK(hipMemcpy(c, cvec, sizeof(double) * B * N * nx, hipMemcpyDeviceToHost));
+  if (!Ghat_x && !Ghat_u) return 0;
+  const size_t XX = (size_t)nx * nx, UU = (size_t)nj * nj;
+  if (ql.soft) {   // k_ginv_soft: [B][N][nx nx + nu nu], the u block of the terminal knot unused
+    BUF(double, soft_Gk, (size_t)B * N * (XX + UU));
+    std::vector<double> h((size_t)B * N * (XX + UU));
+    HIP_OK(hipMemcpy(h.data(), soft_Gk, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t b = 0; b < (size_t)B; ++b)
+      for (size_t k = 0; k < (size_t)N; ++k) {
+        const double* s = h.data() + (b * N + k) * (XX + UU);
+        if (Ghat_x) memcpy(Ghat_x + (b * N + k) * XX, s, XX * sizeof(double));
+        if (Ghat_u && k < (size_t)K) memcpy(Ghat_u + (b * K + k) * UU, s + XX, UU * sizeof(double));
+      }
+    return 0;
+  }
+  // k_ginv: [B][3][nx nx] = (Q + rho I)^-1, (QF + rho I)^-1, (R + rho I)^-1 packed at stride nu; knot k reads the
+  // QF block at the terminal knot and from QF_start on (use_QF)
+  BUF(double, Ginv, (size_t)B * 3 * XX);
+  std::vector<double> h((size_t)B * 3 * XX);
+  HIP_OK(hipMemcpy(h.data(), Ginv, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (size_t b = 0; b < (size_t)B; ++b)
+    for (size_t k = 0; k < (size_t)N; ++k) {
+      const bool qf = (int)k == N - 1 || (ql.QF_start >= 0 && (int)k >= ql.QF_start);
+      if (Ghat_x) memcpy(Ghat_x + (b * N + k) * XX, h.data() + (b * 3 + (qf ? 1 : 0)) * XX, XX * sizeof(double));
+      if (Ghat_u && k < (size_t)K) memcpy(Ghat_u + (b * K + k) * UU, h.data() + (b * 3 + 2) * XX, UU * sizeof(double));
+    }
   return 0;
 }
 

@@ -64,6 +64,10 @@ struct tmpc_ctx {
   // other user of those buffers (setup_hard) and by a change of the limits, so stale data is refused
   struct { int B, N, dmax, W, rmax; } hard_last{0, 0, 0, 0, 0};   // B = 0: none
   tmpc::HardArgs hard_dev{};              // the hd_* buffers as setup_hard last laid them out
+  // the last tmpc_qp_batch (tmpc_qp_last_inputs reads the buffers its QP consumed: Amat, Bmat, cvec and Ginv or
+  // soft_Gk); cleared by every other user of those buffers (alloc_work), so stale data is refused.  nj, QF_start:
+  // the model and cost of that call, which lay the Ghat blocks out
+  struct { int B, N, nj, QF_start; bool soft, banded; } qp_last{0, 0, 0, -1, false, false};   // B = 0: none
   std::map<std::string, double> kbytes;   // bytes beyond registers / LDS of counting kernels since tmpc_reset_stats
   std::vector<tmpc_ctx*> subs;            // a stream's concurrent sub-streams (tmpc_stream.substreams): own HIP
                                           // stream and buffers each, the configuration copied from this context

@@ -136,6 +136,7 @@ int alloc_work(tmpc_ctx* ctx, int B, int N, Work& w, bool with_blocks) {
   BUF(double, dx, (size_t)B * N * nx);
   BUF(double, du, (size_t)B * K * nj);
   BUF(int, iters, (size_t)B);
+  ctx->qp_last = {0, 0, 0, -1, false, false};   // these buffers are about to be rewritten (tmpc_qp_last_inputs)
   w = Work{};   // everything else null until its user sets it
   w.xs = xs; w.qdd = qdd; w.minv = minv; w.cvec = cvec; w.A = Amat; w.Bm = Bmat; w.G = Ginv;
   w.dx = dx; w.du = du; w.iters = iters;
