@@ -90,7 +90,7 @@ int tmpc_rollout_batch_device(tmpc_ctx* ctx, int B, int N, double dt, double* d_
   if (!ctx->has_model) return fail(ctx, "no model");
   if (int rc = wide_ok(ctx, "dynamics")) return rc;
   hipSetDevice(ctx->device);
-  LAUNCH_OK(launch_rollout(dyn32(ctx), ctx->stream, ctx->hmodel.n, ctx->hmodel.chain != 0, ctx->model_id, ctx->dmodel, B, N, dt, d_x, d_u));
+  LAUNCH_OK(launch_rollout(dyn32(ctx), ctx->stream, model_sel(ctx), Batch{{}, B, N}, dt, d_x, d_u));
   HIP_OK(hipStreamSynchronize(ctx->stream));
   return 0;
 }
@@ -110,8 +110,10 @@ int tmpc_fd_batch(tmpc_ctx* ctx, int K, double dt, const double* x, const double
   BUF(double, u_minv, (size_t)K * nj * nj);
   HIP_OK(hipMemcpyAsync(u_x, x, sizeof(double) * K * nx, hipMemcpyHostToDevice, ctx->stream));
   HIP_OK(hipMemcpyAsync(u_u, u, sizeof(double) * K * nj, hipMemcpyHostToDevice, ctx->stream));
-  LAUNCH_OK(launch_unit_fd(dyn32(ctx), ctx->stream, nj, ctx->hmodel.chain != 0, ctx->model_id, ctx->dmodel, K, dt, u_x, u_u, u_xn, u_qdd));
-  if (Minv) LAUNCH_OK(launch_unit_minv(dyn32(ctx), ctx->stream, nj, ctx->hmodel.chain != 0, ctx->model_id, ctx->dmodel, K, u_x, u_minv));
+  DynArgs a{};
+  a.K = K; a.dt = dt; a.x = u_x; a.u = u_u; a.xnext = u_xn; a.qdd = u_qdd; a.minv = u_minv;
+  LAUNCH_OK(launch_unit_fd(dyn32(ctx), ctx->stream, model_sel(ctx), a));
+  if (Minv) LAUNCH_OK(launch_unit_minv(dyn32(ctx), ctx->stream, model_sel(ctx), a));
   HIP_OK(hipStreamSynchronize(ctx->stream));
   if (xnext) HIP_OK(hipMemcpy(xnext, u_xn, sizeof(double) * K * nx, hipMemcpyDeviceToHost));
   if (qdd) HIP_OK(hipMemcpy(qdd, u_qdd, sizeof(double) * K * nj, hipMemcpyDeviceToHost));
@@ -127,7 +129,6 @@ int tmpc_fd_grad_batch(tmpc_ctx* ctx, int K, double dt, const double* x, const d
   if (K < 1) return 0;
   hipSetDevice(ctx->device);
   const int nj = ctx->hmodel.n, nx = 2 * nj;
-  const bool chain = ctx->hmodel.chain != 0;
   BUF(double, u_x, (size_t)K * nx);
   BUF(double, u_u, (size_t)K * nj);
   BUF(double, u_qdd, (size_t)K * nj);
@@ -137,9 +138,13 @@ int tmpc_fd_grad_batch(tmpc_ctx* ctx, int K, double dt, const double* x, const d
   BUF(double, u_dqdd, (size_t)K * nj * 3 * nj);
   HIP_OK(hipMemcpyAsync(u_x, x, sizeof(double) * K * nx, hipMemcpyHostToDevice, ctx->stream));
   HIP_OK(hipMemcpyAsync(u_u, u, sizeof(double) * K * nj, hipMemcpyHostToDevice, ctx->stream));
-  LAUNCH_OK(launch_unit_fd(dyn32(ctx), ctx->stream, nj, chain, ctx->model_id, ctx->dmodel, K, 0.0, u_x, u_u, nullptr, u_qdd));
-  LAUNCH_OK(launch_unit_minv(dyn32(ctx), ctx->stream, nj, chain, ctx->model_id, ctx->dmodel, K, u_x, u_minv));
-  LAUNCH_OK(launch_unit_grad(dyn32(ctx), ctx->stream, nj, chain, ctx->model_id, ctx->dmodel, K, dt, u_x, u_qdd, u_minv, u_A, u_B, u_dqdd));
+  const ModelSel m = model_sel(ctx);
+  DynArgs a{};   // no xnext: the accelerations only
+  a.K = K; a.x = u_x; a.u = u_u; a.qdd = u_qdd; a.minv = u_minv; a.A = u_A; a.Bm = u_B; a.dqdd = u_dqdd;
+  LAUNCH_OK(launch_unit_fd(dyn32(ctx), ctx->stream, m, a));
+  LAUNCH_OK(launch_unit_minv(dyn32(ctx), ctx->stream, m, a));
+  a.dt = dt;
+  LAUNCH_OK(launch_unit_grad(dyn32(ctx), ctx->stream, m, a));
   HIP_OK(hipStreamSynchronize(ctx->stream));
   if (A) HIP_OK(hipMemcpy(A, u_A, sizeof(double) * K * nx * nx, hipMemcpyDeviceToHost));
   if (Bo) HIP_OK(hipMemcpy(Bo, u_B, sizeof(double) * K * nx * nj, hipMemcpyDeviceToHost));
@@ -177,7 +182,7 @@ int tmpc_qp_batch(tmpc_ctx* ctx, int B, int N, double dt, int linsys, const doub
   HIP_OK(hipMemcpyAsync(st.rho, rho, sizeof(double) * B, hipMemcpyHostToDevice, ctx->stream));
   ProbState st0 = st;   // the initial state of a solve, but for rho: the caller's
   st0.rho = st.drho;
-  launch_init_state(ctx->stream, B, 0.0, st0, nullptr);
+  launch_init_state(ctx->stream, B, 0.0, st0);
   if (xs)   // the SQP's initial state (solveKKTSystem_Schur's xs argument, :361): c_0 = x_0 - xs
     HIP_OK(hipMemcpyAsync(w.xs, xs, sizeof(double) * B * nx, hipMemcpyHostToDevice, ctx->stream));
   else
@@ -199,9 +204,9 @@ int tmpc_qp_batch(tmpc_ctx* ctx, int B, int N, double dt, int linsys, const doub
     w.hard = &hard;
   }
   ctx->hard_last = {0, 0, 0, 0, 0};
-  if ((rc = goal_window(ctx, B, N, B, "batch size", nullptr, 0, nullptr, &w.gw))) return rc;   // tmpc_set_reference
-  if ((rc = run_qp(ctx, B, N, dt, precond, io_x, io_u, st, w, !banded, PList{nullptr, nullptr}, B)))
-    return rc;
+  if ((rc = goal_window(ctx, B, N, B, "batch size", nullptr, 0, nullptr, &w.qp.gw))) return rc;   // tmpc_set_reference
+  bind_work(ctx, N, dt, io_x, io_u, st, w);
+  if ((rc = run_qp(ctx, B, precond, st, w, !banded, PList{}, B))) return rc;
   HIP_OK(hipStreamSynchronize(ctx->stream));
   if (banded) {
     if ((rc = collect_hard_work(ctx, hard))) return rc;
@@ -215,13 +220,13 @@ int tmpc_qp_batch(tmpc_ctx* ctx, int B, int N, double dt, int linsys, const doub
     HIP_OK(hipMemcpy(w.lam, lr.data(), lr.size() * sizeof(double), hipMemcpyHostToDevice));
   }
   resolve_timings(ctx);
-  ctx->qp_last = {B, N, nj, ctx->hcost.QF_start, w.jsoft != nullptr, banded};   // tmpc_qp_last_inputs
+  ctx->qp_last = {B, N, nj, ctx->hcost.QF_start, w.qp.jsoft != nullptr, banded};   // tmpc_qp_last_inputs
   if (dxul) {
     std::vector<double> lam((size_t)B * N * nx);
     HIP_OK(hipMemcpy(lam.data(), w.lam, lam.size() * sizeof(double), hipMemcpyDeviceToHost));
-    if ((rc = download_dxul(ctx, B, N, nx, nj, w.dx, w.du, lam.data(), dxul))) return rc;
+    if ((rc = download_dxul(ctx, B, N, nx, nj, w.qp.dx, w.qp.du, lam.data(), dxul))) return rc;
   }
-  if (pcg_iters) HIP_OK(hipMemcpy(pcg_iters, w.iters, sizeof(int) * B, hipMemcpyDeviceToHost));
+  if (pcg_iters) HIP_OK(hipMemcpy(pcg_iters, w.qp.iters, sizeof(int) * B, hipMemcpyDeviceToHost));
   if (S_diag) HIP_OK(hipMemcpy(S_diag, w.Sd, sizeof(double) * B * N * nx * nx, hipMemcpyDeviceToHost));
   if (S_lo) HIP_OK(hipMemcpy(S_lo, w.Sl, sizeof(double) * B * K * nx * nx, hipMemcpyDeviceToHost));
   if (gamma) HIP_OK(hipMemcpy(gamma, w.gam, sizeof(double) * B * N * nx, hipMemcpyDeviceToHost));
@@ -303,23 +308,24 @@ int tmpc_ilqr_step_batch(tmpc_ctx* ctx, int B, int N, double dt, const double* x
   HIP_OK(hipMemcpyAsync(st.rho, rho, sizeof(double) * B, hipMemcpyHostToDevice, ctx->stream));
   ProbState st0 = st;   // the initial state of a solve (every problem active), but for rho: the caller's
   st0.rho = st.drho;
-  launch_init_state(ctx->stream, B, 0.0, st0, nullptr);
+  launch_init_state(ctx->stream, B, 0.0, st0);
   HIP_OK(hipGetLastError());
   // xs = x[:, 0]: the trajectory is taken as given (no rollout), so the defects run_dynamics also forms are unused
   HIP_OK(hipMemcpy2DAsync(w.xs, sizeof(double), io_x, (size_t)N * sizeof(double), sizeof(double), (size_t)B * nx,
                           hipMemcpyDeviceToDevice, ctx->stream));
-  if ((rc = goal_window(ctx, B, N, B, "batch size", nullptr, 0, nullptr, &w.gw))) return rc;   // tmpc_set_reference
-  if ((rc = ilqr_sweeps(ctx, N, dt, io_x, io_u, st, w, PList{nullptr, nullptr}, B, q))) return rc;
+  if ((rc = goal_window(ctx, B, N, B, "batch size", nullptr, 0, nullptr, &w.qp.gw))) return rc;   // tmpc_set_reference
+  bind_work(ctx, N, dt, io_x, io_u, st, w);
+  if ((rc = ilqr_sweeps(ctx, st, w, PList{}, B, q))) return rc;
   HIP_OK(hipStreamSynchronize(ctx->stream));
   resolve_timings(ctx);
-  if (A) HIP_OK(hipMemcpy(A, w.A, sizeof(double) * B * Kn * nx * nx, hipMemcpyDeviceToHost));
-  if (Bm) HIP_OK(hipMemcpy(Bm, w.Bm, sizeof(double) * B * Kn * nx * nj, hipMemcpyDeviceToHost));
+  if (A) HIP_OK(hipMemcpy(A, w.dyn.A, sizeof(double) * B * Kn * nx * nx, hipMemcpyDeviceToHost));
+  if (Bm) HIP_OK(hipMemcpy(Bm, w.dyn.Bm, sizeof(double) * B * Kn * nx * nj, hipMemcpyDeviceToHost));
   if (K) HIP_OK(hipMemcpy(K, q.K, sizeof(double) * B * Kn * nj * nx, hipMemcpyDeviceToHost));
   if (d) HIP_OK(hipMemcpy(d, q.d, sizeof(double) * B * Kn * nj, hipMemcpyDeviceToHost));
   if (dV) HIP_OK(hipMemcpy(dV, q.dV, sizeof(double) * B * 2, hipMemcpyDeviceToHost));
   if (ok) HIP_OK(hipMemcpy(ok, q.ok, sizeof(int) * B, hipMemcpyDeviceToHost));
   if (alphas) HIP_OK(hipMemcpy(alphas, q.alphas, sizeof(double) * T, hipMemcpyDeviceToHost));
-  if (Jt) HIP_OK(hipMemcpy(Jt, q.J, sizeof(double) * B * T, hipMemcpyDeviceToHost));
+  if (Jt) HIP_OK(hipMemcpy(Jt, q.Jt, sizeof(double) * B * T, hipMemcpyDeviceToHost));
   // the trials are knot-major on the device ([B][T][N][nx]): the caller's are the trajectory layout [nx][N]
   if (xt) {
     std::vector<double> h((size_t)B * T * N * nx);
@@ -361,32 +367,29 @@ int tmpc_qp_blocks_batch(tmpc_ctx* ctx, int B, int N, int nx, int nu, int linsys
   const double tol = ctx->opts.exit_tolerance_linSys;
   const int max_iter = ctx->opts.max_iter_linSys;
   const bool keep = S_diag || S_lo || gamma;
+  QpArgs qa{};   // what every phase reads; a phase adds its mode and the outputs it writes
+  qa.B = B; qa.N = N; qa.precond = PRECOND_SS; qa.G = q.Gh; qa.g = q.g; qa.A = q.A; qa.Bm = q.B; qa.cvec = q.c;
+  qa.err = q.err; qa.tol = tol; qa.max_iter = max_iter; qa.iters = q.it; qa.dx = q.dx; qa.du = q.du; qa.lam = hb_lam;
   if (precond == 0) {   // methods S / N: Schur blocks -> block-Thomas -> dxu
     std::vector<int> act(B, 1);
     BUF(int, hb_act, (size_t)B);
     BUF(double, hb_U, (size_t)B * K * nx * nx);
     BUF(double, hb_Y, (size_t)B * N * nx);
     HIP_OK(hipMemcpyAsync(hb_act, act.data(), sizeof(int) * B, hipMemcpyHostToDevice, ctx->stream));
-    {
-      Timed t(ctx, "qp_blocks_schur");
-      LAUNCH_OK(launch_qp_blocks(ctx->stream, nu, B, N, PRECOND_SS, QP_MODE_SCHUR, q.Gh, q.g, q.A, q.B, q.c,
-                                 q.err, tol, max_iter, nullptr, q.it, q.dx, q.du, hb_lam, hb_Sd, hb_Sl, hb_gam));
-    }
-    {
-      Timed t(ctx, "btsolve");
-      LAUNCH_OK(launch_btsolve(ctx->stream, nx, B, N, hb_act, hb_Sd, hb_Sl, hb_gam, hb_U, hb_Y, hb_lam));
-    }
-    {
-      Timed t(ctx, "qp_blocks_dxu");
-      LAUNCH_OK(launch_qp_blocks(ctx->stream, nu, B, N, PRECOND_SS, QP_MODE_DXU, q.Gh, q.g, q.A, q.B, q.c,
-                                 q.err, tol, max_iter, nullptr, q.it, q.dx, q.du, hb_lam, nullptr, nullptr,
-                                 nullptr));
-    }
+    QpArgs a = qa;
+    a.mode = QP_MODE_SCHUR; a.Sd = hb_Sd; a.Sl = hb_Sl; a.gam = hb_gam;
+    { Timed t(ctx, "qp_blocks_schur"); LAUNCH_OK(launch_qp_blocks(ctx->stream, nu, a)); }
+    a.active = hb_act; a.U = hb_U; a.Y = hb_Y;
+    { Timed t(ctx, "btsolve"); LAUNCH_OK(launch_btsolve(ctx->stream, nx, a)); }
+    a = qa;
+    a.mode = QP_MODE_DXU;
+    { Timed t(ctx, "qp_blocks_dxu"); LAUNCH_OK(launch_qp_blocks(ctx->stream, nu, a)); }
   } else {
+    QpArgs a = qa;
+    a.mode = QP_MODE_PCG; a.precond = precond; a.guess = hb_guess;
+    if (keep) { a.Sd = hb_Sd; a.Sl = hb_Sl; a.gam = hb_gam; }
     Timed t(ctx, "qp_blocks");
-    LAUNCH_OK(launch_qp_blocks(ctx->stream, nu, B, N, precond, QP_MODE_PCG, q.Gh, q.g, q.A, q.B, q.c, q.err,
-                               tol, max_iter, hb_guess, q.it, q.dx, q.du, hb_lam, keep ? hb_Sd : nullptr,
-                               keep ? hb_Sl : nullptr, keep ? hb_gam : nullptr));
+    LAUNCH_OK(launch_qp_blocks(ctx->stream, nu, a));
   }
   HIP_OK(hipStreamSynchronize(ctx->stream));
   resolve_timings(ctx);
@@ -632,11 +635,13 @@ int tmpc_pcg_batch(tmpc_ctx* ctx, int B, int N, int nx, int precond, const doubl
     HIP_OK(hipMemcpyAsync(p_Su, S_up, sizeof(double) * B * K * nx * nx, hipMemcpyHostToDevice, ctx->stream));
   HIP_OK(hipMemcpyAsync(p_g, gamma, sizeof(double) * B * N * nx, hipMemcpyHostToDevice, ctx->stream));
   {
+    QpArgs a{};   // the optional inputs and outputs the caller gave
+    a.B = B; a.N = N; a.precond = precond; a.Sd = p_Sd; a.Sl = p_Sl; a.gam = p_g; a.tol = tol; a.max_iter = max_iter;
+    a.lam = p_lam; a.iters = p_it;
+    a.Su = S_up ? p_Su : nullptr; a.guess = guess ? p_x0 : nullptr; a.Pd = P_diag ? p_Pd : nullptr;
+    a.tnu = trace_nu ? p_tn : nullptr; a.tres = trace_res ? p_tr : nullptr;
     Timed t(ctx, "pcg");
-    LAUNCH_OK(launch_pcg(ctx->stream, nx, B, N, precond, p_Sd, p_Sl, S_up ? p_Su : nullptr, p_g,
-                         guess ? p_x0 : nullptr, tol,
-                         max_iter, p_lam, p_it, trace_nu ? p_tn : nullptr, trace_res ? p_tr : nullptr,
-                         P_diag ? p_Pd : nullptr));
+    LAUNCH_OK(launch_pcg(ctx->stream, nx, a));
   }
   HIP_OK(hipStreamSynchronize(ctx->stream));
   resolve_timings(ctx);

@@ -185,6 +185,11 @@ inline bool dyn32(const tmpc_ctx* ctx) { return ctx->opts.precision != TMPC_PREC
 inline bool val32(const tmpc_ctx* ctx) { return ctx->opts.precision == TMPC_PRECISION_MIXED; }
 inline bool ric32(const tmpc_ctx* ctx) { return ctx->opts.precision == TMPC_PRECISION_F32; }
 
+// the model the context's launches run on
+inline ModelSel model_sel(const tmpc_ctx* ctx) {
+  return ModelSel{ctx->hmodel.n, ctx->hmodel.chain != 0, ctx->model_id, ctx->dmodel};
+}
+
 inline SolverOpts solver_opts(const tmpc_options& o) {
   SolverOpts s{};
   s.exit_tol_sqp = o.exit_tolerance_SQP_DDP; s.alpha_factor = o.alpha_factor_SQP_DDP;
@@ -266,19 +271,23 @@ inline bool qp_banded(const tmpc_ctx* ctx, int N) {
 }
 
 // ------------------------------------------------------------------ the solver drivers (tmpc_solve.cpp)
-// Buffers of one QP phase (shared by SQP, iLQR and tmpc_qp_batch)
+// One QP phase (shared by SQP, iLQR and tmpc_qp_batch): the launchers' blocks with what a solve keeps fixed --
+// their buffers (alloc_work; gs and qp.jsoft: init_soft, else null; qp.gw: goal_window), the horizon, trajectory
+// and per-problem masks (bind_work) -- to which run_dynamics / run_qp add the problem list and, per phase, the
+// mode and the outputs it writes from the buffers below
 struct Work {
-  double *xs, *qdd, *minv, *cvec, *A, *Bm, *G, *Sd, *Sl, *gam, *lam, *dx, *du, *Pd;
-  int* iters;
+  DynArgs dyn;
+  QpArgs qp;
+  GinvSoftArgs gs;
+  double* xs;      // the start states [B][nx] (dyn.xs), which the drivers write
+  double *G, *Sd, *Sl, *gam, *lam, *Pd;
   double *U, *Y;   // method S scratch (k_btsolve)
-  double *Gk, *jsoft, *smu, *slam;   // soft limits: per-knot Ghat, jacobian, AL constants
   const double* guess;               // PCG initial iterate [B][N nx] (nullable)
   double* lam_keep;                  // where the PCG path stores lambda (nullable; warm start)
   HardArgs* hard;                    // hard box constraints: the variable-row QP (tmpc_hard.hip)
   double* Sg;                        // S / P^-1 rows in HBM past 1024 rows (k_qp<..., GM>), else null
   unsigned long long* tr_active;     // hard limits: per-QP active-set bitmasks into the trace (nullable)
   int Wtr;                           // trace row stride
-  double* gw;                        // the goal window [B][N][nx] of a tracking solve (goal_window), else null
 };
 
 int alloc_work(tmpc_ctx* ctx, int B, int N, Work& w, bool with_blocks);
@@ -291,29 +300,22 @@ int setup_hard(tmpc_ctx* ctx, int B, int N, int T, int precond, HardArgs& hard, 
                int rmax_given = -1);
 int collect_hard_work(tmpc_ctx* ctx, const HardArgs& hard);
 int run_hard_qp(tmpc_ctx* ctx, int nj, HardArgs& h);
-int run_qp(tmpc_ctx* ctx, int B, int N, double dt, int precond, const double* d_x, const double* d_u,
-           const ProbState& st, Work& w, bool keep_blocks, PList P, int nb);
+// the horizon, step, trajectory and st's masks into w's blocks: once per solve, before run_qp / ilqr_sweeps
+void bind_work(const tmpc_ctx* ctx, int N, double dt, const double* d_x, const double* d_u, const ProbState& st,
+               Work& w);
+int run_qp(tmpc_ctx* ctx, int B, int precond, const ProbState& st, Work& w, bool keep_blocks, PList P, int nb);
 int sqp_device(tmpc_ctx* ctx, int B, int N, double dt, int linsys, double* d_x, double* d_u, TraceDev* tr_out,
                bool keep_warm = false, bool hard_trace = false, const StreamDev* sd = nullptr);
-// One iLQR iteration's sweeps (shared by the iLQR driver and tmpc_ilqr_step_batch): what the backward sweep
-// leaves for the forward one and the T trials' rollouts and costs for the decision.  Trials are knot-major
-// ([B][T][N][nx], [B][T][N-1][nu]: tmpc_ilqr.hip).
-struct IlqrSweep {
-  int T;                       // line-search trials, alpha_list of the options
-  double *alphas;              // [T]
-  double *K, *d, *dV;          // [B][N-1][nu][nx], [B][N-1][nu], [B][2]
-  int* ok;                     // [B]
-  double *xt, *ut, *J;         // [B][T][N][nx], [B][T][N-1][nu], [B][T]
-  double *jac;                 // soft limits: the knots' jacobians [B][N][3 n] (else null)
-  double *smu, *slam, *sphi;   // soft limits: the context's state the sweeps run on (else null)
-};
+// One iLQR iteration's sweeps (shared by the iLQR driver and tmpc_ilqr_step_batch): the launchers' block with the
+// context's cost, limits and soft state (mu, lam), the alphas and the sweeps' buffers set (ilqr_sweep_setup);
+// ilqr_sweeps adds the problems, the trajectory and the dynamics' blocks.
+using IlqrSweep = IlqrArgs;
 // What iLQR refuses (UrdfCost, hard limits, check_ready's wide-model restrictions), then the sweeps' buffers, the
 // soft state (init_soft; fresh: from the limits' initial constants regardless) and the alphas on the stream.
 int ilqr_sweep_setup(tmpc_ctx* ctx, int B, int N, bool fresh_soft, IlqrSweep& q);
 // run_dynamics, the backward sweep, the T rollouts with their costs (soft values included): the problems of
 // P / nb that are st.active, at st.rho
-int ilqr_sweeps(tmpc_ctx* ctx, int N, double dt, const double* d_x, const double* d_u, const ProbState& st,
-                const Work& w, PList P, int nb, const IlqrSweep& q);
+int ilqr_sweeps(tmpc_ctx* ctx, const ProbState& st, const Work& w, PList P, int nb, const IlqrSweep& q);
 int ilqr_device(tmpc_ctx* ctx, int B, int N, double dt, double* d_x, double* d_u, TraceDev* tr_out,
                 const StreamDev* sd = nullptr);
 int stream_solve(tmpc_ctx* ctx, int N, double dt, int linsys, const tmpc_stream* s);
@@ -323,6 +325,6 @@ int mpc_device(tmpc_ctx* ctx, int B, int N, double dt, int solver, int steps, do
 // reference cannot be combined with (UrdfCost; R not 1 or `rows`, the batch size or the stream's period) is
 // refused here.  pid / pbase / mask: a stream's slots (null / 0 / null: problem b, every problem).
 int goal_window(tmpc_ctx* ctx, int B, int N, int rows, const char* rows_name, const int* pid, int pbase,
-                const int* mask, double** gw);
+                const int* mask, const double** gw);
 
 }  // namespace tmpc

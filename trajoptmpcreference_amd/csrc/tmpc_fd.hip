@@ -354,11 +354,10 @@ __global__ void __launch_bounds__(64) k_mpc_shift(MT M, int B, int N, double dt,
 
 template <int NJ, bool CHAIN, class MT>
 struct LaunchFD {
-  static void qp_fd(bool f32, hipStream_t s, const ModelDev* M, PList P, int B, int N, double dt, const double* x,
-                    const double* u, const double* xs, const int* need, double* qdd, double* cvec) {
+  static void qp_fd(bool f32, hipStream_t s, const ModelDev* M, const DynArgs& a) {
     with_real<NJ>(f32, [&](auto r) {
-      hipLaunchKernelGGL((k_qp_fd<NJ, CHAIN, MT, decltype(r)>), TMPC_GRID(B * (N - 1), 256), 0, s, MT::make(M), P, B, N, dt,
-                         x, u, xs, need, qdd, cvec);
+      hipLaunchKernelGGL((k_qp_fd<NJ, CHAIN, MT, decltype(r)>), TMPC_GRID(a.B * (a.N - 1), 256), 0, s, MT::make(M), a.P,
+                         a.B, a.N, a.dt, a.x, a.u, a.xs, a.need, a.qdd, a.cvec);
     });
   }
   // a runtime model (ModelRef) takes the general-topology line-search instance even for a chain: with
@@ -368,96 +367,77 @@ struct LaunchFD {
   static constexpr bool LCHAIN = MT::STATIC ? CHAIN : false;
   // TRK: the tracking instances (a goal window gw), built in their own translation unit (tmpc_fd_trk.hip)
   template <bool TRK>
-  static void ls_terms(bool f32, hipStream_t s, const ModelDev* M, const CostDev* C, const ConstrDev* Cs, const double* mu,
-                       const double* lam, PList P, int B, int N, int T, double dt, const double* alphas, const double* x,
-                       const double* u, const double* xs, const double* dx, const double* du, const int* active,
-                       double* terms, const double* gw) {
-#define TMPC_LS(SOFTV, RV)                                                                                        \
-    hipLaunchKernelGGL((k_ls_terms<NJ, LCHAIN, SOFTV, MT, RV, TRK>), TMPC_GRID(B * T * N, 256), 0, s, MT::make(M), C, Cs, \
-                       mu, lam, P, B, N, T, dt, alphas, x, u, xs, dx, du, active, terms, gw);
+  static void ls_terms(bool f32, hipStream_t s, const ModelDev* M, const LsTermsArgs& a) {
+#define TMPC_LS(SOFTV, RV)                                                                                          \
+    hipLaunchKernelGGL((k_ls_terms<NJ, LCHAIN, SOFTV, MT, RV, TRK>), TMPC_GRID(a.B * a.T * a.N, 256), 0, s, MT::make(M), \
+                       a.C, a.Cs, a.mu, a.lam, a.P, a.B, a.N, a.T, a.dt, a.alphas, a.x, a.u, a.xs, a.dx, a.du, a.active, \
+                       a.terms, a.gw);
     if constexpr (kWide<NJ>) {   // a wide model: fp64 without soft limits only (check_ready refuses the rest)
       TMPC_LS(false, double)
     } else {
-      if (mu) { if (f32) { TMPC_LS(true, float) } else { TMPC_LS(true, double) } }
+      if (a.mu) { if (f32) { TMPC_LS(true, float) } else { TMPC_LS(true, double) } }
       else { if (f32) { TMPC_LS(false, float) } else { TMPC_LS(false, double) } }
     }
 #undef TMPC_LS
   }
-  static void unit_fd(bool f32, hipStream_t s, const ModelDev* M, int K, double dt, const double* x, const double* u,
-                      double* xnext, double* qdd) {
+  static void unit_fd(bool f32, hipStream_t s, const ModelDev* M, const DynArgs& a) {
     with_real<NJ>(f32, [&](auto r) {
-      hipLaunchKernelGGL((k_unit_fd<NJ, CHAIN, MT, decltype(r)>), TMPC_GRID(K, 256), 0, s, MT::make(M), K, dt, x, u, xnext,
-                         qdd);
+      hipLaunchKernelGGL((k_unit_fd<NJ, CHAIN, MT, decltype(r)>), TMPC_GRID(a.K, 256), 0, s, MT::make(M), a.K, a.dt, a.x,
+                         a.u, a.xnext, a.qdd);
     });
   }
-  static void mpc_shift(hipStream_t s, const ModelDev* M, int B, int N, double dt, int step, int steps, double* x,
-                        double* u, double* xe, double* ue) {
-    hipLaunchKernelGGL((k_mpc_shift<NJ, CHAIN, MT>), dim3(B), dim3(64), 0, s, MT::make(M), B, N, dt, step, steps, x,
-                       u, xe, ue);
+  static void mpc_shift(hipStream_t s, const ModelDev* M, const ShiftArgs& a) {
+    hipLaunchKernelGGL((k_mpc_shift<NJ, CHAIN, MT>), dim3(a.B), dim3(64), 0, s, MT::make(M), a.B, a.N, a.dt, a.step,
+                       a.steps, a.x, a.u, a.xe, a.ue);
   }
-  static void rollout(bool f32, hipStream_t s, const ModelDev* M, int B, int N, double dt, double* x, const double* u,
-                      PList P, const int* mask) {
+  static void rollout(bool f32, hipStream_t s, const ModelDev* M, const Batch& b, double dt, double* x, const double* u,
+                      const int* mask) {
     with_real<NJ>(f32, [&](auto r) {
-      hipLaunchKernelGGL((k_rollout<NJ, CHAIN, MT, decltype(r)>), TMPC_GRID(B, 64), 0, s, MT::make(M), P, B, N, dt, x, u,
-                         mask);
+      hipLaunchKernelGGL((k_rollout<NJ, CHAIN, MT, decltype(r)>), TMPC_GRID(b.B, 64), 0, s, MT::make(M), b.P, b.B, b.N,
+                         dt, x, u, mask);
     });
   }
 };
 
 #ifdef TMPC_TRK_PART
-int launch_ls_terms_trk(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, const CostDev* C,
-                        const ConstrDev* Cs, const double* mu, const double* lam, PList P, int B, int N, int T,
-                        double dt, const double* alphas, const double* x, const double* u, const double* xs,
-                        const double* dx, const double* du, const int* active, double* terms, const double* gw) {
-  return dispatch_model(mid, nj, chain, [&](auto t) {
+int launch_ls_terms_trk(bool f32, hipStream_t s, const ModelSel& m, const LsTermsArgs& a) {
+  return dispatch_model(m.mid, m.nj, m.chain, [&](auto t) {
     using Tag = decltype(t);
-    LaunchFD<Tag::nj, Tag::chain, typename Tag::model>::template ls_terms<true>(f32, s, M, C, Cs, mu, lam, P, B, N, T, dt,
-                                                                                alphas, x, u, xs, dx, du, active, terms, gw);
+    LaunchFD<Tag::nj, Tag::chain, typename Tag::model>::template ls_terms<true>(f32, s, m.M, a);
   });
 }
 #else
-int launch_qp_fd(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, PList P, int B, int N,
-                 double dt, const double* x, const double* u, const double* xs, const int* need, double* qdd,
-                 double* cvec) {
-  return dispatch_model(mid, nj, chain, [&](auto t) {
+int launch_qp_fd(bool f32, hipStream_t s, const ModelSel& m, const DynArgs& a) {
+  return dispatch_model(m.mid, m.nj, m.chain, [&](auto t) {
     using T = decltype(t);
-    LaunchFD<T::nj, T::chain, typename T::model>::qp_fd(f32, s, M, P, B, N, dt, x, u, xs, need, qdd, cvec);
+    LaunchFD<T::nj, T::chain, typename T::model>::qp_fd(f32, s, m.M, a);
   });
 }
-int launch_ls_terms(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, const CostDev* C,
-                    const ConstrDev* Cs, const double* mu, const double* lam, PList P, int B, int N, int T, double dt,
-                    const double* alphas, const double* x, const double* u, const double* xs, const double* dx,
-                    const double* du, const int* active, double* terms, const double* gw) {
-  if (gw)
-    return launch_ls_terms_trk(f32, s, nj, chain, mid, M, C, Cs, mu, lam, P, B, N, T, dt, alphas, x, u, xs, dx, du, active,
-                               terms, gw);
-  return dispatch_model(mid, nj, chain, [&](auto t) {
+int launch_ls_terms(bool f32, hipStream_t s, const ModelSel& m, const LsTermsArgs& a) {
+  if (a.gw) return launch_ls_terms_trk(f32, s, m, a);
+  return dispatch_model(m.mid, m.nj, m.chain, [&](auto t) {
     using Tag = decltype(t);
-    LaunchFD<Tag::nj, Tag::chain, typename Tag::model>::template ls_terms<false>(f32, s, M, C, Cs, mu, lam, P, B, N, T, dt,
-                                                                                 alphas, x, u, xs, dx, du, active, terms,
-                                                                                 gw);
+    LaunchFD<Tag::nj, Tag::chain, typename Tag::model>::template ls_terms<false>(f32, s, m.M, a);
   });
 }
-int launch_unit_fd(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, int K, double dt,
-                   const double* x, const double* u, double* xnext, double* qdd) {
-  return dispatch_model(mid, nj, chain, [&](auto t) {
+int launch_unit_fd(bool f32, hipStream_t s, const ModelSel& m, const DynArgs& a) {
+  return dispatch_model(m.mid, m.nj, m.chain, [&](auto t) {
     using T = decltype(t);
-    LaunchFD<T::nj, T::chain, typename T::model>::unit_fd(f32, s, M, K, dt, x, u, xnext, qdd);
+    LaunchFD<T::nj, T::chain, typename T::model>::unit_fd(f32, s, m.M, a);
   });
 }
-int launch_rollout(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, int B, int N, double dt,
-                   double* x, const double* u, PList P, const int* mask) {
-  return dispatch_model(mid, nj, chain, [&](auto t) {
+int launch_rollout(bool f32, hipStream_t s, const ModelSel& m, const Batch& b, double dt, double* x, const double* u,
+                   const int* mask) {
+  return dispatch_model(m.mid, m.nj, m.chain, [&](auto t) {
     using T = decltype(t);
-    LaunchFD<T::nj, T::chain, typename T::model>::rollout(f32, s, M, B, N, dt, x, u, P, mask);
+    LaunchFD<T::nj, T::chain, typename T::model>::rollout(f32, s, m.M, b, dt, x, u, mask);
   });
 }
 
-int launch_mpc_shift(hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, int B, int N, double dt, int step,
-                     int steps, double* x, double* u, double* xe, double* ue) {
-  return dispatch_model(mid, nj, chain, [&](auto t) {
+int launch_mpc_shift(hipStream_t s, const ModelSel& m, const ShiftArgs& a) {
+  return dispatch_model(m.mid, m.nj, m.chain, [&](auto t) {
     using T = decltype(t);
-    LaunchFD<T::nj, T::chain, typename T::model>::mpc_shift(s, M, B, N, dt, step, steps, x, u, xe, ue);
+    LaunchFD<T::nj, T::chain, typename T::model>::mpc_shift(s, m.M, a);
   });
 }
 

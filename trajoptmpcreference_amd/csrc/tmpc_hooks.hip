@@ -304,30 +304,27 @@ struct LaunchHooks {
     constexpr int n = 3 * NJ;
     hipLaunchKernelGGL((k_ghat_full<n>), dim3(B * N), dim3(64), 0, s, B, N, 2 * NJ, NJ, G, rho, Gh, err);
   }
-  static void qp(hipStream_t s, int B, int N, int precond, int mode, const double* Gh, const double* g,
-                const double* A, const double* Bm, const double* c, const int* err, double tol, int max_iter,
-                const double* guess, int* iters, double* dx, double* du, double* lam, double* Sd, double* Sl,
-                double* gam) {
+  static void qp(hipStream_t s, const QpArgs& a) {
     constexpr int NX = 2 * NJ;
-    const int rows = N * NX;
-    const int rpl = pcg_rpl(N, NX);
+    const int rows = a.N * NX;
+    const int rpl = pcg_rpl(a.N, NX);
     const int threads = ((rows / rpl + 63) / 64) * 64;
-    const size_t lds = qpb_lds_doubles(N, NX, NJ) * sizeof(double);
-#define TMPC_QPB_ARGS s, B, N, precond, Gh, g, A, Bm, c, err, tol, max_iter, guess, iters, dx, du, lam, Sd, Sl, gam
-#define TMPC_QPB_LAUNCH(MD)                                                                                  \
-    if (rpl == 1)                                                                                            \
-      hipLaunchKernelGGL((k_qp_blocks<NJ, 1, 768, MD>), dim3(B), dim3(threads), lds, TMPC_QPB_ARGS);         \
-    else                                                                                                     \
-      hipLaunchKernelGGL((k_qp_blocks<NJ, 2, 512, MD>), dim3(B), dim3(threads), lds, TMPC_QPB_ARGS);
-    if (mode == QP_MODE_PCG) {
+    const size_t lds = qpb_lds_doubles(a.N, NX, NJ) * sizeof(double);
+    auto go = [&](auto* kernel) {
+      hipLaunchKernelGGL(kernel, dim3(a.B), dim3(threads), lds, s, a.B, a.N, a.precond, a.G, a.g, a.A, a.Bm, a.cvec, a.err,
+                         a.tol, a.max_iter, a.guess, a.iters, a.dx, a.du, a.lam, a.Sd, a.Sl, a.gam);
+    };
+#define TMPC_QPB_LAUNCH(MD)                     \
+    if (rpl == 1) go(k_qp_blocks<NJ, 1, 768, MD>); \
+    else go(k_qp_blocks<NJ, 2, 512, MD>);
+    if (a.mode == QP_MODE_PCG) {
       TMPC_QPB_LAUNCH(QP_MODE_PCG)
-    } else if (mode == QP_MODE_SCHUR) {
+    } else if (a.mode == QP_MODE_SCHUR) {
       TMPC_QPB_LAUNCH(QP_MODE_SCHUR)
     } else {
       TMPC_QPB_LAUNCH(QP_MODE_DXU)
     }
 #undef TMPC_QPB_LAUNCH
-#undef TMPC_QPB_ARGS
   }
   static int set_lds(int bytes) {
     int e = 0;
@@ -345,17 +342,11 @@ int launch_ghat_full(hipStream_t s, int nj, int B, int N, const double* G, const
   return for_nj<1, NJ_FULL>(nj, [&](auto n) { LaunchHooks<decltype(n)::value>::ghat(s, B, N, G, rho, Gh, err); });
 }
 
-int launch_qp_blocks(hipStream_t s, int nj, int B, int N, int precond, int mode, const double* Gh, const double* g,
-                     const double* A, const double* Bm, const double* c, const int* err, double tol, int max_iter,
-                     const double* guess, int* iters, double* dx, double* du, double* lam, double* Sd, double* Sl,
-                     double* gam) {
-  const int rows = N * 2 * nj;
+int launch_qp_blocks(hipStream_t s, int nj, const QpArgs& a) {
+  const int rows = a.N * 2 * nj;
   if (rows > 1024) return -1;
-  if (qpb_lds_doubles(N, 2 * nj, nj) * sizeof(double) > 160 * 1024) return -3;
-  return for_nj<1, NJ_FULL>(nj, [&](auto n) {
-    LaunchHooks<decltype(n)::value>::qp(s, B, N, precond, mode, Gh, g, A, Bm, c, err, tol, max_iter, guess, iters, dx,
-                                        du, lam, Sd, Sl, gam);
-  });
+  if (qpb_lds_doubles(a.N, 2 * nj, nj) * sizeof(double) > 160 * 1024) return -3;
+  return for_nj<1, NJ_FULL>(nj, [&](auto n) { LaunchHooks<decltype(n)::value>::qp(s, a); });
 }
 
 int qp_blocks_set_max_lds() {

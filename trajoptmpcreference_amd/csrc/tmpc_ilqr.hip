@@ -1169,86 +1169,79 @@ template <int NJ>
 struct LaunchIlqrNJ {
   // TRK: the tracking instances (a goal window gw), built in their own translation unit (tmpc_ilqr_trk.hip)
   template <bool TRK>
-  static void backward(bool f32, hipStream_t s, const CostDev* C, const ConstrDev* Cs, PList P, int B, int N, const double* x,
-                       const double* u, const double* rho, const int* active, const double* A, const double* Bm,
-                       const double* mu, const double* lam, double* jscratch, double* K, double* d, double* dV,
-                       int* ok, const double* gw) {
-#define TMPC_BWD(RV, MFV, JS)                                                                                          \
-    hipLaunchKernelGGL((k_ilqr_backward<NJ, RV, MFV, TRK>), dim3(B), dim3(64), 0, s, C, Cs, P, B, N, x, u, rho, active, A, \
-                       Bm, mu, lam, JS, K, d, dV, ok, gw);
+  static void backward(bool f32, hipStream_t s, const IlqrArgs& a) {
+    auto go = [&](auto* kernel, const double* js) {
+      hipLaunchKernelGGL(kernel, dim3(a.B), dim3(64), 0, s, a.C, a.Cs, a.P, a.B, a.N, a.x, a.u, a.rho, a.active, a.A, a.Bm,
+                         a.mu, a.lam, js, a.K, a.d, a.dV, a.ok, a.gw);
+    };
     if constexpr (kWide<NJ>) {   // a wide model: fp64 VALU sweep, no soft limits (check_ready refuses the rest)
-      TMPC_BWD(double, false, nullptr)
+      go(k_ilqr_backward<NJ, double, false, TRK>, nullptr);
     } else {
       // fp64: the matrix-core products (MF) unless TMPC_ILQR_VALU=1 (the VALU loops, for comparison)
       const char* v = getenv("TMPC_ILQR_VALU");
       const bool mf = !(v && v[0] == '1');
       // soft limits: every knot's jacobian first, in parallel ([B][N][3 NJ] in jscratch)
       const double* js = nullptr;
-      if (mu) {
-        hipLaunchKernelGGL((k_ilqr_soft_jac<NJ>), TMPC_GRID(B * N, 256), 0, s, Cs, mu, lam, P, B, N, x, u, active, jscratch);
-        js = jscratch;
+      if (a.mu) {
+        hipLaunchKernelGGL((k_ilqr_soft_jac<NJ>), TMPC_GRID(a.B * a.N, 256), 0, s, a.Cs, a.mu, a.lam, a.P, a.B, a.N, a.x, a.u,
+                           a.active, a.jscratch);
+        js = a.jscratch;
       }
       // fp32: the Riccati state in fp32; its Q products on the matrix cores from the fp32 operands (fp64 MFMA
       // accumulation, rounded to fp32) unless TMPC_ILQR_F32_VALU=1 (the fp32 VALU loops)
       const char* fv = getenv("TMPC_ILQR_F32_VALU");
       const bool f32mf = mf && !(fv && fv[0] == '1');
-      if (f32 && f32mf) { TMPC_BWD(float, true, js) }
-      else if (f32) { TMPC_BWD(float, false, js) }
-      else if (mf) { TMPC_BWD(double, true, js) }
-      else { TMPC_BWD(double, false, js) }
+      if (f32 && f32mf) go(k_ilqr_backward<NJ, float, true, TRK>, js);
+      else if (f32) go(k_ilqr_backward<NJ, float, false, TRK>, js);
+      else if (mf) go(k_ilqr_backward<NJ, double, true, TRK>, js);
+      else go(k_ilqr_backward<NJ, double, false, TRK>, js);
     }
-#undef TMPC_BWD
   }
   template <bool TRK>
-  static void init_cost(hipStream_t s, const CostDev* C, const ConstrDev* Cs, const double* mu, const double* lam, PList P,
-                        int B, int N, const double* x, const double* u, const int* mask, double* Jt, const double* gw) {
-    const size_t lds = (size_t)2 * N * sizeof(double);
-#define TMPC_INITC(SOFTV)                                                                                              \
-    hipLaunchKernelGGL((k_ilqr_init_cost<NJ, SOFTV, TRK>), dim3(B), dim3(64), lds, s, C, Cs, mu, lam, P, B, N, x, u, mask, \
-                       Jt, gw);
+  static void init_cost(hipStream_t s, const IlqrArgs& a) {
+    const size_t lds = (size_t)2 * a.N * sizeof(double);
+    auto go = [&](auto* kernel) {
+      hipLaunchKernelGGL(kernel, dim3(a.B), dim3(64), lds, s, a.C, a.Cs, a.mu, a.lam, a.P, a.B, a.N, a.x, a.u, a.active,
+                         a.Jt, a.gw);
+    };
     if constexpr (!kWide<NJ>) {   // a wide model: no soft limits (launch_ilqr_init_cost refuses them)
-      if (mu) {
-        TMPC_INITC(true)
+      if (a.mu) {
+        go(k_ilqr_init_cost<NJ, true, TRK>);
         return;
       }
     }
-    TMPC_INITC(false)
-#undef TMPC_INITC
+    go(k_ilqr_init_cost<NJ, false, TRK>);
   }
 };
 
 template <int NJ, bool CHAIN, class MT>
 struct LaunchIlqr {
   template <bool TRK>
-  static void forward(bool f32, hipStream_t s, const ModelDev* M, const CostDev* C, const ConstrDev* Cs, const double* mu,
-                      const double* lam, PList P, int B, int N, int T, double dt, int init, const double* alphas,
-                      const double* x, const double* u, const double* K, const double* d, const int* active,
-                      const int* ok, double* xt, double* ut, double* Jt, const double* gw) {
+  static void forward(bool f32, hipStream_t s, const ModelDev* M, const IlqrArgs& a) {
     // the prefetching instance when its LDS buffers fit (T >= 2: <= 33 problems per group); init
     // evaluations (no feedback law) take the plain one.  TMPC_ILQR_NOPF=1: plain only (comparison)
     const char* npf = getenv("TMPC_ILQR_NOPF");
-    const size_t pf_lds = FwdPf<NJ, TRK>::lds_doubles(T) * sizeof(double);
-    const bool pf = !init && pf_lds <= 48 * 1024 && !(npf && npf[0] == '1');
+    const size_t pf_lds = FwdPf<NJ, TRK>::lds_doubles(a.T) * sizeof(double);
+    const bool pf = !a.init && pf_lds <= 48 * 1024 && !(npf && npf[0] == '1');
+    auto go = [&](auto* kernel, size_t lds) {
+      hipLaunchKernelGGL(kernel, TMPC_GRID(a.B * a.T, 64), lds, s, MT::make(M), a.C, a.Cs, a.mu, a.lam, a.P, a.B, a.N, a.T,
+                         a.dt, a.init, a.alphas, a.x, a.u, a.K, a.d, a.active, a.ok, a.xt, a.ut, a.Jt, a.gw);
+    };
     if constexpr (kWide<NJ>) {   // a wide model: fp64, no soft limits, the plain (non-prefetching) instance
-      hipLaunchKernelGGL((k_ilqr_forward<NJ, CHAIN, false, MT, double, false, TRK>), TMPC_GRID(B * T, 64), 0, s,
-                         MT::make(M), C, Cs, mu, lam, P, B, N, T, dt, init, alphas, x, u, K, d, active, ok, xt, ut, Jt, gw);
+      go(k_ilqr_forward<NJ, CHAIN, false, MT, double, false, TRK>, 0);
       return;
     } else {
-#define TMPC_FWD(SOFTV, RV)                                                                                          \
-    if (pf)                                                                                                          \
-      hipLaunchKernelGGL((k_ilqr_forward<NJ, CHAIN, SOFTV, MT, RV, true, TRK>), TMPC_GRID(B * T, 64), pf_lds, s,      \
-                         MT::make(M), C, Cs, mu, lam, P, B, N, T, dt, init, alphas, x, u, K, d, active, ok, xt, ut, Jt, gw); \
-    else                                                                                                             \
-      hipLaunchKernelGGL((k_ilqr_forward<NJ, CHAIN, SOFTV, MT, RV, false, TRK>), TMPC_GRID(B * T, 64), 0, s, MT::make(M), \
-                         C, Cs, mu, lam, P, B, N, T, dt, init, alphas, x, u, K, d, active, ok, xt, ut, Jt, gw);
+#define TMPC_FWD(SOFTV, RV)                                                      \
+    if (pf) go(k_ilqr_forward<NJ, CHAIN, SOFTV, MT, RV, true, TRK>, pf_lds);     \
+    else go(k_ilqr_forward<NJ, CHAIN, SOFTV, MT, RV, false, TRK>, 0);
     // soft limits: the rollouts sum the cost terms, k_ilqr_soft_add the soft values (INIT: in the kernel)
-    if (mu && init) { if (f32) { TMPC_FWD(true, float) } else { TMPC_FWD(true, double) } }
+    if (a.mu && a.init) { if (f32) { TMPC_FWD(true, float) } else { TMPC_FWD(true, double) } }
     else { if (f32) { TMPC_FWD(false, float) } else { TMPC_FWD(false, double) } }
 #undef TMPC_FWD
-    if (mu && !init) {
-      const int tg = soft_add_group(T, N);
-      hipLaunchKernelGGL((k_ilqr_soft_add<NJ>), dim3(B), dim3(64), (size_t)tg * (N + 1) * sizeof(double), s, Cs, mu, lam,
-                         P, B, N, T, tg, xt, ut, active, ok, Jt);
+    if (a.mu && !a.init) {
+      const int tg = soft_add_group(a.T, a.N);
+      hipLaunchKernelGGL((k_ilqr_soft_add<NJ>), dim3(a.B), dim3(64), (size_t)tg * (a.N + 1) * sizeof(double), s, a.Cs, a.mu,
+                         a.lam, a.P, a.B, a.N, a.T, tg, a.xt, a.ut, a.active, a.ok, a.Jt);
     }
     }
   }
@@ -1264,63 +1257,39 @@ constexpr bool kTrkPart = true;
 constexpr bool kTrkPart = false;
 #endif
 
-int TMPC_TRK_FN(launch_ilqr_backward)(bool f32, hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, PList P,
-                                      int B, int N, const double* x, const double* u, const double* rho,
-                                      const int* active, const double* A, const double* Bm, const double* mu,
-                                      const double* lam, double* jscratch, double* K, double* d, double* dV, int* ok,
-                                      const double* gw) {
+int TMPC_TRK_FN(launch_ilqr_backward)(bool f32, hipStream_t s, int nj, const IlqrArgs& a) {
 #ifndef TMPC_TRK_PART
-  if (gw)
-    return launch_ilqr_backward_trk(f32, s, nj, C, Cs, P, B, N, x, u, rho, active, A, Bm, mu, lam, jscratch, K, d, dV, ok,
-                                    gw);
+  if (a.gw) return launch_ilqr_backward_trk(f32, s, nj, a);
 #endif
-  return for_nj<1, NJMAX>(nj, [&](auto n) {
-    LaunchIlqrNJ<decltype(n)::value>::template backward<kTrkPart>(f32, s, C, Cs, P, B, N, x, u, rho, active, A, Bm, mu,
-                                                                  lam, jscratch, K, d, dV, ok, gw);
-  });
+  return for_nj<1, NJMAX>(nj, [&](auto n) { LaunchIlqrNJ<decltype(n)::value>::template backward<kTrkPart>(f32, s, a); });
 }
 
 // (Unlike tmpc_fd.hip / tmpc_kernels.hip, a runtime chain model keeps the CHAIN instance here: the rollout
 // measured 2.1 ms per launch on it against 3.2 ms on the general-topology one, arm6 B = 4096.)
-int TMPC_TRK_FN(launch_ilqr_forward)(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M,
-                                     const CostDev* C, const ConstrDev* Cs, const double* mu, const double* lam,
-                                     PList P, int B, int N, int T, double dt, int init, const double* alphas,
-                                     const double* x, const double* u, const double* K, const double* d,
-                                     const int* active, const int* ok, double* xt, double* ut, double* Jt,
-                                     const double* gw) {
+int TMPC_TRK_FN(launch_ilqr_forward)(bool f32, hipStream_t s, const ModelSel& m, const IlqrArgs& a) {
 #ifndef TMPC_TRK_PART
-  if (gw)
-    return launch_ilqr_forward_trk(f32, s, nj, chain, mid, M, C, Cs, mu, lam, P, B, N, T, dt, init, alphas, x, u, K, d,
-                                   active, ok, xt, ut, Jt, gw);
+  if (a.gw) return launch_ilqr_forward_trk(f32, s, m, a);
 #endif
-  return dispatch_model(mid, nj, chain, [&](auto t) {
+  return dispatch_model(m.mid, m.nj, m.chain, [&](auto t) {
     using Tag = decltype(t);
-    LaunchIlqr<Tag::nj, Tag::chain, typename Tag::model>::template forward<kTrkPart>(
-        f32, s, M, C, Cs, mu, lam, P, B, N, T, dt, init, alphas, x, u, K, d, active, ok, xt, ut, Jt, gw);
+    LaunchIlqr<Tag::nj, Tag::chain, typename Tag::model>::template forward<kTrkPart>(f32, s, m.M, a);
   });
 }
 
-int TMPC_TRK_FN(launch_ilqr_init_cost)(hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, const double* mu,
-                                       const double* lam, PList P, int B, int N, const double* x, const double* u,
-                                       const int* mask, double* Jt, const double* gw) {
-  if ((size_t)2 * N * sizeof(double) > 64 * 1024) return -1;
-  if (nj > NJ_FULL && mu) return -2;   // a wide model: no soft limits
+int TMPC_TRK_FN(launch_ilqr_init_cost)(hipStream_t s, int nj, const IlqrArgs& a) {
+  if ((size_t)2 * a.N * sizeof(double) > 64 * 1024) return -1;
+  if (nj > NJ_FULL && a.mu) return -2;   // a wide model: no soft limits
 #ifndef TMPC_TRK_PART
-  if (gw) return launch_ilqr_init_cost_trk(s, nj, C, Cs, mu, lam, P, B, N, x, u, mask, Jt, gw);
+  if (a.gw) return launch_ilqr_init_cost_trk(s, nj, a);
 #endif
-  return for_nj<1, NJMAX>(nj, [&](auto n) {
-    LaunchIlqrNJ<decltype(n)::value>::template init_cost<kTrkPart>(s, C, Cs, mu, lam, P, B, N, x, u, mask, Jt, gw);
-  });
+  return for_nj<1, NJMAX>(nj, [&](auto n) { LaunchIlqrNJ<decltype(n)::value>::template init_cost<kTrkPart>(s, a); });
 }
 #undef TMPC_TRK_FN
 
 #ifndef TMPC_TRK_PART
-void launch_ilqr_decide(hipStream_t s, PList P, int B, int N, int NX, int NU, int T, int init, const double* alphas,
-                        const SolverOpts& o, const double* Jt, const double* dV, const int* ok, const double* xt,
-                        const double* ut, double* x, double* u, const ProbState& st, const TraceDev& tr,
-                        int* active_count, unsigned long long* counters, int* activate) {
-  hipLaunchKernelGGL(k_ilqr_decide, dim3(B), dim3(64), 0, s, P, B, N, NX, NU, T, init, alphas, o, Jt, dV, ok, xt, ut, x,
-                     u, st, tr, active_count, counters, activate);
+void launch_ilqr_decide(hipStream_t s, const DecideArgs& a) {
+  hipLaunchKernelGGL(k_ilqr_decide, dim3(a.B), dim3(64), 0, s, a.P, a.B, a.N, a.NX, a.NU, a.T, a.init, a.alphas, a.o, a.Jt,
+                     a.dV, a.ok, a.xt, a.ut, a.x, a.u, a.st, a.tr, a.active_count, a.counters, a.activate);
 }
 
 #endif   // TMPC_TRK_PART

@@ -30,7 +30,7 @@ struct PList {
   __device__ __forceinline__ int at(int p) const { return idx ? idx[p] : p; }
   __device__ __forceinline__ bool has(int p, int nb) const { return p < nb && (!cnt || p < *cnt); }
 };
-void launch_alive_list(hipStream_t s, int B, const int* alive, int* idx, int* cnt, int* host_slot);
+void launch_alive_list(hipStream_t s, int B, const int* alive, int* idx, int* cnt, int* host_slot = nullptr);
 
 // PRECOND_NONE: the identity preconditioner '0' (PCG.py:114-118)
 enum { PRECOND_J = 1, PRECOND_BJ = 2, PRECOND_SS = 3, PRECOND_NONE = 4 };
@@ -84,47 +84,103 @@ struct TraceDev {
   unsigned long long* hard_active;   // [B][W][N] per-knot active-set bitmasks of the QP (nullable)
 };
 
-// f32: rigid-body dynamics (and, for launch_ilqr_backward, the Riccati sweep) in fp32 --
-// tmpc_options.precision F32 / MIXED; every buffer stays fp64
-int launch_qp_fd(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, PList P, int B, int N, double dt, const double* x,
-                 const double* u, const double* xs, const int* need, double* qdd, double* cvec);
-int launch_qp_minv(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, PList P, int B, int N, const double* x,
-                   const int* need, double* minv);
-int launch_qp_grad(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, PList P, int B, int N, double dt, const double* x,
-                   const int* need, const double* qdd, const double* minv, double* A, double* Bm);
-int launch_ls_terms(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, const CostDev* C, const ConstrDev* Cs,
-                    const double* mu, const double* lam, PList P, int B, int N, int T, double dt, const double* alphas,
-                    const double* x, const double* u, const double* xs, const double* dx, const double* du,
-                    const int* active, double* terms, const double* gw = nullptr);
+// the model a launch runs on (tmpc_ctx.h model_sel); mid 0: the runtime model, whose coefficients M holds
+struct ModelSel { int nj; bool chain; int mid; const ModelDev* M; };
+// the problems a launch visits (PList above, B its bound) and the horizon
+struct Batch { PList P; int B, N; };
+
+// The launchers' argument blocks: a caller value-initialises one (`Args a{};`: pointers null, the PList the
+// identity), fills it by name and passes it by const&.  A field is named as the kernel parameter it feeds.
+// f32: the dynamics (launch_ilqr_backward: the Riccati sweep) in fp32, tmpc_options.precision; buffers stay fp64
+
+// the dynamics of the problems that need fresh gradients (run_dynamics' three launches)
+struct DynArgs : Batch {
+  double dt;
+  const double *x, *u, *xs;
+  const int* need;
+  // launch_qp_fd: qdd (where the gradient is taken), the defects cvec; launch_qp_minv: minv; launch_qp_grad: A, Bm
+  double *qdd, *cvec, *minv, *A, *Bm;
+  // the unit entry points (launch_unit_*: tmpc_fd_batch, tmpc_fd_grad_batch) read K states x [K][nx], u [K][nu] in
+  // place of the Batch, xs, need and cvec; launch_unit_fd writes qdd and xnext (nullable), launch_unit_grad dqdd too
+  int K;
+  double *xnext, *dqdd;
+};
+int launch_qp_fd(bool f32, hipStream_t s, const ModelSel& m, const DynArgs& a);
+int launch_qp_minv(bool f32, hipStream_t s, const ModelSel& m, const DynArgs& a);
+int launch_qp_grad(bool f32, hipStream_t s, const ModelSel& m, const DynArgs& a);
+// the line search's per-knot merit terms [B][T][N][4] of the T trials x - alphas[t] dx, u - alphas[t] du
+struct LsTermsArgs : Batch {
+  const CostDev* C;
+  const ConstrDev* Cs;
+  const double *mu, *lam;   // the soft limits' state (null: none)
+  int T;
+  double dt;
+  const double *alphas, *x, *u, *xs;
+  const double *dx, *du;    // null: the terms at x, u themselves (the initial merit)
+  const int* active;
+  double* terms;
+  const double* gw;         // the goal window of a tracking solve (below), else null
+};
+int launch_ls_terms(bool f32, hipStream_t s, const ModelSel& m, const LsTermsArgs& a);
 // The goal window (tmpc_set_reference): gw [B][N][nx], knot-major -- the state goal of problem b's knot k, which
 // the tracking instances of the goal-reading kernels (their TRK template argument) read in place of CostDev::xg.
 // A null gw launches the fixed-goal instances, which are the kernels as they were.  launch_goal_window resolves
 // the reference xref [R][nx][M] for one horizon solve: gw[b][k] = xref[(pbase + (pid ? pid[b] : b)) % R]
 // [:, min(k + step, M - 1)], for the problems in `mask` (null: all; a stream's slot with pid < 0 is skipped).
-void launch_goal_window(hipStream_t s, int B, int N, int nx, int R, int M, int step, const double* xref,
-                        const int* pid, int pbase, const int* mask, double* gw);
+struct GoalWindowArgs {
+  int B, N, nx, R, M, step, pbase;
+  const double* xref;
+  const int *pid, *mask;
+  double* gw;
+};
+void launch_goal_window(hipStream_t s, const GoalWindowArgs& a);
 // (the launchers of the tracking instances, which live in translation units of their own: tmpc_fd_trk.hip,
 // tmpc_ilqr_trk.hip; launch_ls_terms / launch_ilqr_* call them when gw is set)
-int launch_ls_terms_trk(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, const CostDev* C, const ConstrDev* Cs,
-                        const double* mu, const double* lam, PList P, int B, int N, int T, double dt, const double* alphas,
-                        const double* x, const double* u, const double* xs, const double* dx, const double* du,
-                        const int* active, double* terms, const double* gw);
-int launch_unit_fd(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, int K, double dt, const double* x,
-                   const double* u, double* xnext, double* qdd);
-int launch_unit_minv(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, int K, const double* x, double* minv);
-int launch_unit_grad(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, int K, double dt, const double* x,
-                     const double* qdd, const double* minv, double* A, double* Bm, double* dqdd);
-// P / mask: the problems to roll out (the identity and every problem by default; the stream's refilled
+int launch_ls_terms_trk(bool f32, hipStream_t s, const ModelSel& m, const LsTermsArgs& a);
+int launch_unit_fd(bool f32, hipStream_t s, const ModelSel& m, const DynArgs& a);
+int launch_unit_minv(bool f32, hipStream_t s, const ModelSel& m, const DynArgs& a);
+int launch_unit_grad(bool f32, hipStream_t s, const ModelSel& m, const DynArgs& a);
+// b / mask: the problems to roll out (the identity and every problem by default; the stream's refilled
 // slots: the alive list and act_init)
-int launch_rollout(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, int B, int N, double dt, double* x,
-                   const double* u, PList P = PList{nullptr, nullptr}, const int* mask = nullptr);
+int launch_rollout(bool f32, hipStream_t s, const ModelSel& m, const Batch& b, double dt, double* x, const double* u,
+                   const int* mask = nullptr);
 int launch_ginv(hipStream_t s, int nj, const CostDev* C, PList P, int B, const double* rho, const int* active, double* G);
-// dt: the Euler step of A_k / B_k (their structural rows are not read, tmpc_kernels.hip qp_schur_row)
-int launch_qp(hipStream_t s, int nj, const CostDev* C, PList P, int B, int N, double dt, int precond, int mode,
-              const double* x, const double* u,
-              const int* active, const double* G, const double* A, const double* Bm, const double* cvec, double tol,
-              int max_iter, int* iters, double* dx, double* du, double* lam, double* Sd, double* Sl, double* gam,
-              double* Pd, const double* jsoft, const double* guess, double* Sg, const double* gw = nullptr);
+// The QP family's block, grouped by the launchers that read a field.  launch_qp (k_qp): mode SCHUR writes Sd / Sl /
+// gam, DXU reads lam and writes dx / du, PCG does all three around its PCG (outputs Sd, Sl, gam, Pd nullable).
+struct QpArgs : Batch {
+  // every launcher: the Schur system S lam = gam (launch_btsolve: of every problem b < B, it takes no problem list)
+  double *Sd, *Sl, *gam, *lam;
+  // launch_qp, launch_qp_blocks, launch_pcg
+  int precond;
+  double tol;
+  int max_iter;
+  const double* guess;     // PCG initial iterate [B][N nx] (nullable)
+  int* iters;
+  // launch_qp, launch_qp_blocks
+  int mode;
+  const double* G;         // (Q + rho I)^-1 blocks [B][3][nx nx] (k_ginv); with jsoft the per-knot Gk (k_ginv_soft)
+  const double *A, *Bm, *cvec;
+  double *dx, *du;
+  // launch_qp only
+  const CostDev* C;
+  double dt;      // the Euler step of A_k / B_k (their structural rows are not read, tmpc_kernels.hip qp_schur_row)
+  const double *x, *u;
+  const int* active;       // launch_btsolve too
+  const double* jsoft;     // soft limits: the knots' jacobian terms (else null)
+  double* Sg;              // S / P^-1 rows in HBM scratch (the GM instances below), else null
+  const double* gw;
+  double* Pd;              // launch_pcg too: the preconditioner's diagonal blocks (nullable)
+  // launch_qp_blocks only (the plugin-hook QP on caller-formed blocks, tmpc_hooks.hip): G holds full
+  // (G_k + rho I)^-1 blocks with launch_ghat_full's per-problem pivot flags err, cvec the caller's c, g its gradient
+  const double* g;
+  const int* err;
+  // launch_pcg only (the stand-alone PCG, tmpc_pcg_batch): the upper blocks (null: Sl's transposes), iteration traces
+  const double* Su;
+  double *tnu, *tres;
+  // launch_btsolve only (method S: the direct block-tridiagonal solve): scratch
+  double *U, *Y;
+};
+int launch_qp(hipStream_t s, int nj, const QpArgs& a);
 // largest Schur dimension N nx of the fused QP: up to 1024 rows S / P^-1 stay in registers, up to
 // QP_MAX_ROWS (the GM kernels: two rows per lane, 12 waves = 3 per SIMD, i.e. 168 VGPRs) in HBM
 // scratch Sg of qp_gm_doubles(B, N, nx) doubles.  1536 = arm6 at N = 128 (BASELINE config 5).
@@ -137,21 +193,22 @@ inline int qp_gm_min_rows() {
   const int v = e ? atoi(e) : 0;
   return v > 0 ? v : 1025;
 }
-int launch_ginv_soft(hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, PList P, int B, int N, const double* rho,
-                     const int* active, const double* x, const double* u, const double* mu, const double* lam,
-                     double* Gk, double* jsoft);
-int launch_pcg(hipStream_t s, int nx, int B, int N, int precond, const double* Sd, const double* Sl,
-               const double* Su, const double* gam, const double* guess, double tol, int max_iter, double* lam,
-               int* iters, double* tnu, double* tres, double* Pd);
+// soft limits: the per-knot Ghat blocks and jacobian terms of the QP, at the soft state mu / lam
+struct GinvSoftArgs : Batch {
+  const CostDev* C;
+  const ConstrDev* Cs;
+  const double* rho;
+  const int* active;
+  const double *x, *u, *mu, *lam;
+  double *Gk, *jsoft;
+};
+int launch_ginv_soft(hipStream_t s, int nj, const GinvSoftArgs& a);
+int launch_pcg(hipStream_t s, int nx, const QpArgs& a);
 // plugin-hook QP on caller-formed blocks (tmpc_hooks.hip)
 int launch_ghat_full(hipStream_t s, int nj, int B, int N, const double* G, const double* rho, double* Gh, int* err);
-int launch_qp_blocks(hipStream_t s, int nj, int B, int N, int precond, int mode, const double* Gh, const double* g,
-                     const double* A, const double* Bm, const double* c, const int* err, double tol, int max_iter,
-                     const double* guess, int* iters, double* dx, double* du, double* lam, double* Sd, double* Sl,
-                     double* gam);
+int launch_qp_blocks(hipStream_t s, int nj, const QpArgs& a);
 int qp_blocks_set_max_lds();
-int launch_btsolve(hipStream_t s, int nx, int B, int N, const int* active, const double* Sd, const double* Sl,
-                   const double* gam, double* U, double* Y, double* lam);
+int launch_btsolve(hipStream_t s, int nx, const QpArgs& a);
 int pcg_set_max_lds();
 void launch_sum_counters(hipStream_t s, int B, const unsigned long long* pc, unsigned long long* out);
 // Continuous batching (tmpc_sqp_solve_stream_device / tmpc_ilqr_solve_stream_device): B resident slots
@@ -175,54 +232,89 @@ struct StreamDev {
 };
 void launch_stream_init(hipStream_t s, int B, const StreamDev& sd, double* x, double* u);
 
-void launch_ls_decide(hipStream_t s, PList P, int B, int N, int NX, int NU, int T, int mode, int soft, const double* alphas,
-                      const SolverOpts& o, const double* terms, double* x, double* u, const double* dx,
-                      const double* du, const ProbState& st, const int* pcg_iters, const TraceDev& tr,
-                      int* active_count, unsigned long long* counters, const double* hterms,
-                      const int* qp_singular = nullptr, int* activate = nullptr);   // activate: as launch_ilqr_decide
-void launch_init_state(hipStream_t s, int B, double rho_init, const ProbState& st, const int* outer_active);
-// st / act_init / rho_init: the per-problem outer loop (null act_init: lock-step, tmpc_kernels.hip);
-// sd / xs / tr / lam_warm: a stream's hand-over of finished slots (nullable; per-problem mode only)
-void launch_soft_outer(hipStream_t s, const ConstrDev* Cs, PList P, int B, int N, int nj, double tol, int max_iter,
-                       double* x, double* u, double* mu, double* lam, double* phi, int* outer_active,
-                       int* outer_iter, int* exit_soft, int* outer_count, const ProbState* st = nullptr,
-                       int* act_init = nullptr, double rho_init = 0.0, const StreamDev* sd = nullptr,
-                       double* xs = nullptr, const TraceDev* tr = nullptr, double* lam_warm = nullptr);
+// the decision that ends an iteration: a trial into x, u, the problem's state and trace, the count of live problems
+struct DecideArgs : Batch {
+  int NX, NU, T;
+  const double* alphas;
+  SolverOpts o;
+  double *x, *u;
+  ProbState st;
+  TraceDev tr;
+  int* active_count;
+  unsigned long long* counters;   // [B][3] per-problem tallies (iterations, -, fresh gradients): launch_sum_counters
+  int* activate;   // initial merit / cost only, nullable: the real active flags -- st.active is then the act_init
+                   // mask, cleared as the problem enters its inner loop
+  // launch_ls_decide
+  int mode, soft;
+  const double *terms, *dx, *du;
+  const int* pcg_iters;
+  const double* hterms;     // hard limits: the violation terms of launch_hard phase 3 (else null)
+  const int* qp_singular;   // HardArgs.sing of the direct banded solve (else null)
+  // launch_ilqr_decide
+  int init;
+  const double *Jt, *dV, *xt, *ut;
+  const int* ok;
+};
+void launch_ls_decide(hipStream_t s, const DecideArgs& a);
 
+// outer_active (nullable): only the problems still in their outer loop
+void launch_init_state(hipStream_t s, int B, double rho_init, const ProbState& st,
+                       const int* outer_active = nullptr);
+struct SoftOuterArgs : Batch {
+  const ConstrDev* Cs;
+  int nj;
+  double tol;
+  int max_iter;
+  double *x, *u, *mu, *lam, *phi;
+  int *outer_active, *outer_iter, *exit_soft, *outer_count;
+  // the per-problem outer loop (null act_init: lock-step, tmpc_kernels.hip)
+  ProbState st;
+  int* act_init;
+  double rho_init;
+  // a stream's hand-over of finished slots (sd.P = 0: none; per-problem mode only)
+  StreamDev sd;
+  double* xs;
+  TraceDev tr;
+  double* lam_warm;
+};
+void launch_soft_outer(hipStream_t s, const SoftOuterArgs& a);
 
-int launch_ilqr_backward(bool f32, hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, PList P, int B, int N, const double* x,
-                         const double* u, const double* rho, const int* active, const double* A, const double* Bm,
-                         const double* mu, const double* lam, double* jscratch, double* K, double* d, double* dV,
-                         int* ok, const double* gw = nullptr);
-int launch_ilqr_forward(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, const CostDev* C, const ConstrDev* Cs,
-                        const double* mu, const double* lam, PList P, int B, int N, int T, double dt, int init,
-                        const double* alphas, const double* x, const double* u, const double* K, const double* d,
-                        const int* active, const int* ok, double* xt, double* ut, double* Jt,
-                        const double* gw = nullptr);
-int launch_ilqr_init_cost(hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, const double* mu,
-                          const double* lam, PList P, int B, int N, const double* x, const double* u, const int* mask,
-                          double* Jt, const double* gw = nullptr);
-int launch_ilqr_backward_trk(bool f32, hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, PList P, int B, int N,
-                             const double* x, const double* u, const double* rho, const int* active, const double* A,
-                             const double* Bm, const double* mu, const double* lam, double* jscratch, double* K,
-                             double* d, double* dV, int* ok, const double* gw);
-int launch_ilqr_forward_trk(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, const CostDev* C,
-                            const ConstrDev* Cs, const double* mu, const double* lam, PList P, int B, int N, int T,
-                            double dt, int init, const double* alphas, const double* x, const double* u, const double* K,
-                            const double* d, const int* active, const int* ok, double* xt, double* ut, double* Jt,
-                            const double* gw);
-int launch_ilqr_init_cost_trk(hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, const double* mu,
-                              const double* lam, PList P, int B, int N, const double* x, const double* u,
-                              const int* mask, double* Jt, const double* gw);
-// counters: per-problem tallies [B][3] (problem-iterations, -, fresh gradients), summed by
-// launch_sum_counters; activate (init only, nullable): the real active flags -- st.active is then the
-// act_init mask, cleared as the problem enters its inner loop
-void launch_ilqr_decide(hipStream_t s, PList P, int B, int N, int NX, int NU, int T, int init, const double* alphas,
-                        const SolverOpts& o, const double* Jt, const double* dV, const int* ok, const double* xt,
-                        const double* ut, double* x, double* u, const ProbState& st, const TraceDev& tr,
-                        int* active_count, unsigned long long* counters, int* activate = nullptr);
-int launch_mpc_shift(hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, int B, int N, double dt, int step,
-                     int steps, double* x, double* u, double* xe, double* ue);
+// One iLQR iteration's sweeps: what the backward sweep leaves for the forward one and the T trials' rollouts and
+// costs for the decision.  Trials are knot-major ([B][T][N][nx], [B][T][N-1][nu]: tmpc_ilqr.hip).
+struct IlqrArgs : Batch {
+  const CostDev* C;
+  const ConstrDev* Cs;
+  const double *mu, *lam;      // the soft limits' state the sweeps run on (null: none)
+  int T;                       // line-search trials, alpha_list of the options
+  double dt;
+  int init;                    // launch_ilqr_forward: the cost of x, u themselves (no feedback law, T = 1)
+  const double* alphas;        // [T]
+  const double *x, *u, *rho;
+  const int* active;           // launch_ilqr_init_cost: its mask
+  const double *A, *Bm;
+  double* jscratch;            // soft limits: the knots' jacobians [B][N][3 n] (else null)
+  double *K, *d, *dV;          // [B][N-1][nu][nx], [B][N-1][nu], [B][2]
+  int* ok;                     // [B]
+  double *xt, *ut, *Jt;        // [B][T][N][nx], [B][T][N-1][nu], [B][T]
+  const double* gw;
+};
+int launch_ilqr_backward(bool f32, hipStream_t s, int nj, const IlqrArgs& a);
+int launch_ilqr_forward(bool f32, hipStream_t s, const ModelSel& m, const IlqrArgs& a);
+int launch_ilqr_init_cost(hipStream_t s, int nj, const IlqrArgs& a);
+int launch_ilqr_backward_trk(bool f32, hipStream_t s, int nj, const IlqrArgs& a);
+int launch_ilqr_forward_trk(bool f32, hipStream_t s, const ModelSel& m, const IlqrArgs& a);
+int launch_ilqr_init_cost_trk(hipStream_t s, int nj, const IlqrArgs& a);
+
+void launch_ilqr_decide(hipStream_t s, const DecideArgs& a);
+// the MPC step: x_0, u_0 through the plant into xe / ue [.. ][steps (+ 1)], the trajectory shifted by one knot
+struct ShiftArgs {
+  int B, N;
+  double dt;
+  int step, steps;
+  double *x, *u, *xe, *ue;
+};
+int launch_mpc_shift(hipStream_t s, const ModelSel& m, const ShiftArgs& a);
+
 void launch_soft_shift(hipStream_t s, const ConstrDev* Cs, int B, int N, int nj, double* mu, double* lam,
                        double* phi);
 void launch_outer_init(hipStream_t s, int B, int* outer_active, int* outer_iter, int* exit_soft);

@@ -912,11 +912,12 @@ __global__ void __launch_bounds__(64) k_btsolve(int N, const int* __restrict__ a
   }
 }
 
-int launch_btsolve(hipStream_t s, int nx, int B, int N, const int* active, const double* Sd, const double* Sl,
-                   const double* gam, double* U, double* Y, double* lam) {
+int launch_btsolve(hipStream_t s, int nx, const QpArgs& a) {
   switch (nx) {
-#define CASE_BT(V) \
-  case V: hipLaunchKernelGGL((k_btsolve<V>), dim3(B), dim3(64), 0, s, N, active, Sd, Sl, gam, U, Y, lam); return 0;
+#define CASE_BT(V)                                                                                                    \
+  case V:                                                                                                             \
+    hipLaunchKernelGGL((k_btsolve<V>), dim3(a.B), dim3(64), 0, s, a.N, a.active, a.Sd, a.Sl, a.gam, a.U, a.Y, a.lam); \
+    return 0;
     CASE_BT(2) CASE_BT(4) CASE_BT(6) CASE_BT(8) CASE_BT(10) CASE_BT(12) CASE_BT(14)
     CASE_BT(16) CASE_BT(18) CASE_BT(20) CASE_BT(22) CASE_BT(24)
 #undef CASE_BT
@@ -1170,34 +1171,32 @@ __global__ void __launch_bounds__(256) k_unit_grad(MT M, int K, double dt,
 // f32: the dynamics in fp32 (tmpc_options.precision F32 / MIXED), fp64 in and out
 template <int NJ, bool CHAIN, class MT>
 struct Launch {
-  static void qp_minv(bool f32, hipStream_t s, const ModelDev* M, PList P, int B, int N, const double* x,
-                      const int* need, double* minv) {
+  static void qp_minv(bool f32, hipStream_t s, const ModelDev* M, const DynArgs& a) {
     with_real<NJ>(f32, [&](auto r) {
-      hipLaunchKernelGGL((k_qp_minv<NJ, CHAIN, MT, decltype(r)>), TMPC_GRID(B * (N - 1) * NJ, 256), 0, s, MT::make(M), P,
-                         B, N, x, need, minv);
+      hipLaunchKernelGGL((k_qp_minv<NJ, CHAIN, MT, decltype(r)>), TMPC_GRID(a.B * (a.N - 1) * NJ, 256), 0, s, MT::make(M),
+                         a.P, a.B, a.N, a.x, a.need, a.minv);
     });
   }
   // a runtime model (ModelRef) takes the general-topology gradient instance even for a chain: with runtime
   // coefficients the chain specialisation's unrolled recursion spills 2.5x more (k_qp_grad<6, chain,
   // ModelRef, double> 4.4 kB per lane against 1.7 kB; 2.7 -> 1.3 ms per headline launch)
   static constexpr bool GCHAIN = MT::STATIC ? CHAIN : false;
-  static void qp_grad(bool f32, hipStream_t s, const ModelDev* M, PList P, int B, int N, double dt, const double* x,
-                      const int* need, const double* qdd, const double* minv, double* A, double* Bm) {
+  static void qp_grad(bool f32, hipStream_t s, const ModelDev* M, const DynArgs& a) {
     with_real<NJ>(f32, [&](auto r) {
-      hipLaunchKernelGGL((k_qp_grad<NJ, GCHAIN, MT, decltype(r)>), TMPC_GRID(B * (N - 1) * 2 * NJ, 256), 0, s,
-                         MT::make(M), P, B, N, dt, x, need, qdd, minv, A, Bm);
+      hipLaunchKernelGGL((k_qp_grad<NJ, GCHAIN, MT, decltype(r)>), TMPC_GRID(a.B * (a.N - 1) * 2 * NJ, 256), 0, s,
+                         MT::make(M), a.P, a.B, a.N, a.dt, a.x, a.need, a.qdd, a.minv, a.A, a.Bm);
     });
   }
-  static void unit_minv(bool f32, hipStream_t s, const ModelDev* M, int K, const double* x, double* minv) {
+  static void unit_minv(bool f32, hipStream_t s, const ModelDev* M, const DynArgs& a) {
     with_real<NJ>(f32, [&](auto r) {
-      hipLaunchKernelGGL((k_unit_minv<NJ, CHAIN, MT, decltype(r)>), TMPC_GRID(K * NJ, 256), 0, s, MT::make(M), K, x, minv);
+      hipLaunchKernelGGL((k_unit_minv<NJ, CHAIN, MT, decltype(r)>), TMPC_GRID(a.K * NJ, 256), 0, s, MT::make(M), a.K, a.x,
+                         a.minv);
     });
   }
-  static void unit_grad(bool f32, hipStream_t s, const ModelDev* M, int K, double dt, const double* x, const double* qdd,
-                        const double* minv, double* A, double* Bm, double* dqdd) {
+  static void unit_grad(bool f32, hipStream_t s, const ModelDev* M, const DynArgs& a) {
     with_real<NJ>(f32, [&](auto r) {
-      hipLaunchKernelGGL((k_unit_grad<NJ, GCHAIN, MT, decltype(r)>), TMPC_GRID(K * 2 * NJ, 256), 0, s, MT::make(M), K, dt,
-                         x, qdd, minv, A, Bm, dqdd);
+      hipLaunchKernelGGL((k_unit_grad<NJ, GCHAIN, MT, decltype(r)>), TMPC_GRID(a.K * 2 * NJ, 256), 0, s, MT::make(M), a.K,
+                         a.dt, a.x, a.qdd, a.minv, a.A, a.Bm, a.dqdd);
     });
   }
 };
@@ -1210,63 +1209,54 @@ struct LaunchNJ {
     else
       hipLaunchKernelGGL((k_ginv<NJ>), TMPC_GRID(B * 3 * 16, 64), 0, s, C, P, B, rho, active, G);
   }
-  static void qp(hipStream_t s, const CostDev* C, PList P, int B, int N, double dt, int precond, int mode, const double* x,
-                 const double* u,
-                 const int* active, const double* G, const double* A, const double* Bm, const double* cvec, double tol,
-                 int max_iter, int* iters, double* dx, double* du, double* lam, double* Sd, double* Sl, double* gam,
-                 double* Pd, const double* jsoft, const double* guess, double* Sg, const double* gw) {
+  static void qp(hipStream_t s, const QpArgs& a) {
     constexpr int NX = 2 * NJ;
-    const int rows = N * NX;
+    const int rows = a.N * NX;
     // S / P^-1 rows in HBM (Sg), two rows per lane, up to 1024 lanes (method S past 1024 rows runs the
     // same instance for its prologue / epilogue modes, which never touch Sg)
-    const bool gm = !kWide<NJ> && (rows > 1024 || (rows >= qp_gm_min_rows() && mode == QP_MODE_PCG));
-    const int rpl = gm ? 2 : pcg_rpl(N, NX);
+    const bool gm = !kWide<NJ> && (rows > 1024 || (rows >= qp_gm_min_rows() && a.mode == QP_MODE_PCG));
+    const int rpl = gm ? 2 : pcg_rpl(a.N, NX);
     const int threads = ((rows / rpl + 63) / 64) * 64;
-    const size_t lds = qp_lds_doubles(N, NX, NJ, gm ? QP_MAX_ROWS : 1024) * sizeof(double);
-#define TMPC_QP_ARGS s, C, P, B, N, dt, precond, x, u, active, G, A, Bm, cvec, tol, max_iter, iters, dx, du, lam, Sd, \
-                     Sl, gam, Pd, jsoft, guess, Sg, gw
-#define TMPC_QP_LAUNCH_T(PKV, MODEV, TRKV)                                                                \
-    if (gm)                                                                                                \
-      hipLaunchKernelGGL((k_qp<NJ, 2, QP_MAX_ROWS / 2, PKV, MODEV, true, TRKV>), dim3(B), dim3(threads), lds, TMPC_QP_ARGS); \
-    else if (rpl == 1)                                                                                     \
-      hipLaunchKernelGGL((k_qp<NJ, 1, 768, PKV, MODEV, false, TRKV>), dim3(B), dim3(threads), lds, TMPC_QP_ARGS); \
-    else                                                                                                   \
-      hipLaunchKernelGGL((k_qp<NJ, 2, 512, PKV, MODEV, false, TRKV>), dim3(B), dim3(threads), lds, TMPC_QP_ARGS);
+    const size_t lds = qp_lds_doubles(a.N, NX, NJ, gm ? QP_MAX_ROWS : 1024) * sizeof(double);
+    auto go = [&](auto* kernel) {
+      hipLaunchKernelGGL(kernel, dim3(a.B), dim3(threads), lds, s, a.C, a.P, a.B, a.N, a.dt, a.precond, a.x, a.u, a.active,
+                         a.G, a.A, a.Bm, a.cvec, a.tol, a.max_iter, a.iters, a.dx, a.du, a.lam, a.Sd, a.Sl, a.gam, a.Pd,
+                         a.jsoft, a.guess, a.Sg, a.gw);
+    };
+#define TMPC_QP_LAUNCH_T(PKV, MODEV, TRKV)                                  \
+    if (gm) go(k_qp<NJ, 2, QP_MAX_ROWS / 2, PKV, MODEV, true, TRKV>);       \
+    else if (rpl == 1) go(k_qp<NJ, 1, 768, PKV, MODEV, false, TRKV>);       \
+    else go(k_qp<NJ, 2, 512, PKV, MODEV, false, TRKV>);
     // a goal window (gw): the tracking instances
-#define TMPC_QP_LAUNCH(PKV, MODEV)                                                                        \
-    if (gw) { TMPC_QP_LAUNCH_T(PKV, MODEV, true) } else { TMPC_QP_LAUNCH_T(PKV, MODEV, false) }
+#define TMPC_QP_LAUNCH(PKV, MODEV) \
+    if (a.gw) { TMPC_QP_LAUNCH_T(PKV, MODEV, true) } else { TMPC_QP_LAUNCH_T(PKV, MODEV, false) }
     if constexpr (kWide<NJ>) {   // a wide model: registers / two rows per lane, no soft limits (launch_qp checks)
-#define TMPC_QP_LAUNCH_WT(MODEV, TRKV)                                                                     \
-      if (rpl == 1)                                                                                        \
-        hipLaunchKernelGGL((k_qp<NJ, 1, 768, false, MODEV, false, TRKV>), dim3(B), dim3(threads), lds, TMPC_QP_ARGS); \
-      else                                                                                                 \
-        hipLaunchKernelGGL((k_qp<NJ, 2, 512, false, MODEV, false, TRKV>), dim3(B), dim3(threads), lds, TMPC_QP_ARGS);
-#define TMPC_QP_LAUNCH_W(MODEV) if (gw) { TMPC_QP_LAUNCH_WT(MODEV, true) } else { TMPC_QP_LAUNCH_WT(MODEV, false) }
-      if (mode == QP_MODE_PCG) { TMPC_QP_LAUNCH_W(QP_MODE_PCG) }
-      else if (mode == QP_MODE_SCHUR) { TMPC_QP_LAUNCH_W(QP_MODE_SCHUR) }
+#define TMPC_QP_LAUNCH_WT(MODEV, TRKV)                                      \
+      if (rpl == 1) go(k_qp<NJ, 1, 768, false, MODEV, false, TRKV>);        \
+      else go(k_qp<NJ, 2, 512, false, MODEV, false, TRKV>);
+#define TMPC_QP_LAUNCH_W(MODEV) if (a.gw) { TMPC_QP_LAUNCH_WT(MODEV, true) } else { TMPC_QP_LAUNCH_WT(MODEV, false) }
+      if (a.mode == QP_MODE_PCG) { TMPC_QP_LAUNCH_W(QP_MODE_PCG) }
+      else if (a.mode == QP_MODE_SCHUR) { TMPC_QP_LAUNCH_W(QP_MODE_SCHUR) }
       else { TMPC_QP_LAUNCH_W(QP_MODE_DXU) }
 #undef TMPC_QP_LAUNCH_W
 #undef TMPC_QP_LAUNCH_WT
     } else {
       // soft limits (jsoft != null): per-knot Ghat from HBM
-      if (mode == QP_MODE_PCG) {
-        if (jsoft) { TMPC_QP_LAUNCH(true, QP_MODE_PCG) } else { TMPC_QP_LAUNCH(false, QP_MODE_PCG) }
-      } else if (mode == QP_MODE_SCHUR) {
-        if (jsoft) { TMPC_QP_LAUNCH(true, QP_MODE_SCHUR) } else { TMPC_QP_LAUNCH(false, QP_MODE_SCHUR) }
+      if (a.mode == QP_MODE_PCG) {
+        if (a.jsoft) { TMPC_QP_LAUNCH(true, QP_MODE_PCG) } else { TMPC_QP_LAUNCH(false, QP_MODE_PCG) }
+      } else if (a.mode == QP_MODE_SCHUR) {
+        if (a.jsoft) { TMPC_QP_LAUNCH(true, QP_MODE_SCHUR) } else { TMPC_QP_LAUNCH(false, QP_MODE_SCHUR) }
       } else {
-        if (jsoft) { TMPC_QP_LAUNCH(true, QP_MODE_DXU) } else { TMPC_QP_LAUNCH(false, QP_MODE_DXU) }
+        if (a.jsoft) { TMPC_QP_LAUNCH(true, QP_MODE_DXU) } else { TMPC_QP_LAUNCH(false, QP_MODE_DXU) }
       }
     }
 #undef TMPC_QP_LAUNCH
 #undef TMPC_QP_LAUNCH_T
-#undef TMPC_QP_ARGS
   }
-  static void ginv_soft(hipStream_t s, const CostDev* C, const ConstrDev* Cs, PList P, int B, int N, const double* rho,
-                        const int* active, const double* x, const double* u, const double* mu, const double* lam,
-                        double* Gk, double* jsoft) {
-    const int wpp = (2 * N + 4 * GINV_SOFT_GROUPS - 1) / (4 * GINV_SOFT_GROUPS);
-    hipLaunchKernelGGL((k_ginv_soft<NJ>), dim3(B * wpp), dim3(64), 0, s, C, Cs, P, B, N, rho, active, x, u, mu, lam, Gk,
-                       jsoft);
+  static void ginv_soft(hipStream_t s, const GinvSoftArgs& a) {
+    const int wpp = (2 * a.N + 4 * GINV_SOFT_GROUPS - 1) / (4 * GINV_SOFT_GROUPS);
+    hipLaunchKernelGGL((k_ginv_soft<NJ>), dim3(a.B * wpp), dim3(64), 0, s, a.C, a.Cs, a.P, a.B, a.N, a.rho, a.active, a.x,
+                       a.u, a.mu, a.lam, a.Gk, a.jsoft);
   }
 };
 
@@ -1305,42 +1295,33 @@ int pcg_set_max_lds() {
 }
 
 template <int NX>
-static void launch_pcg_nx(hipStream_t s, int B, int N, int precond, const double* Sd, const double* Sl,
-                          const double* Su, const double* gam, const double* guess, double tol, int max_iter,
-                          double* lam, int* iters, double* tnu, double* tres, double* Pd) {
-  const int rows = N * NX;
-  const int rpl = pcg_rpl(N, NX);
+static void launch_pcg_nx(hipStream_t s, const QpArgs& a) {
+  const int rows = a.N * NX;
+  const int rpl = pcg_rpl(a.N, NX);
   const int threads = ((rows / rpl + 63) / 64) * 64;
-  const size_t lds = pcg_lds_doubles(N, NX, 1024) * sizeof(double);
-  if (rpl == 1)
-    hipLaunchKernelGGL((k_pcg<NX, 1, 768>), dim3(B), dim3(threads), lds, s, B, N, precond, Sd, Sl, Su, gam, guess,
-                       tol, max_iter, lam, iters, tnu, tres, Pd);
-  else
-    hipLaunchKernelGGL((k_pcg<NX, 2, 512>), dim3(B), dim3(threads), lds, s, B, N, precond, Sd, Sl, Su, gam, guess,
-                       tol, max_iter, lam, iters, tnu, tres, Pd);
+  const size_t lds = pcg_lds_doubles(a.N, NX, 1024) * sizeof(double);
+  auto go = [&](auto* kernel) {
+    hipLaunchKernelGGL(kernel, dim3(a.B), dim3(threads), lds, s, a.B, a.N, a.precond, a.Sd, a.Sl, a.Su, a.gam, a.guess,
+                       a.tol, a.max_iter, a.lam, a.iters, a.tnu, a.tres, a.Pd);
+  };
+  if (rpl == 1) go(k_pcg<NX, 1, 768>);
+  else go(k_pcg<NX, 2, 512>);
 }
 
-int launch_pcg(hipStream_t s, int nx, int B, int N, int precond, const double* Sd, const double* Sl,
-               const double* Su, const double* gam, const double* guess, double tol, int max_iter, double* lam,
-               int* iters, double* tnu, double* tres, double* Pd) {
-  if (N * nx > 1024) return -1;
-  return for_nj<2, PCG_NX_MAX, 2>(nx, [&](auto v) {
-    launch_pcg_nx<decltype(v)::value>(s, B, N, precond, Sd, Sl, Su, gam, guess, tol, max_iter, lam, iters, tnu, tres, Pd);
-  });
+int launch_pcg(hipStream_t s, int nx, const QpArgs& a) {
+  if (a.N * nx > 1024) return -1;
+  return for_nj<2, PCG_NX_MAX, 2>(nx, [&](auto v) { launch_pcg_nx<decltype(v)::value>(s, a); });
 }
 
-void launch_ls_decide(hipStream_t s, PList P, int B, int N, int NX, int NU, int T, int mode, int soft,
-                      const double* alphas, const SolverOpts& o, const double* terms, double* x, double* u,
-                      const double* dx, const double* du, const ProbState& st, const int* pcg_iters,
-                      const TraceDev& tr, int* active_count, unsigned long long* counters, const double* hterms,
-                      const int* qp_singular, int* activate) {
+void launch_ls_decide(hipStream_t s, const DecideArgs& a) {
   // LDS staging of the terms up to LS_DECIDE_STAGE_MAX bytes (within the default dynamic-LDS limit; N = 64,
   // T = 9: 18 kB), the direct HBM walks past it
   constexpr size_t LS_DECIDE_STAGE_MAX = 60 * 1024;
-  size_t stage = ((size_t)T * N * 4 + (hterms ? (size_t)T * N : 0)) * sizeof(double);
+  size_t stage = ((size_t)a.T * a.N * 4 + (a.hterms ? (size_t)a.T * a.N : 0)) * sizeof(double);
   if (stage > LS_DECIDE_STAGE_MAX) stage = 0;
-  hipLaunchKernelGGL(k_ls_decide, dim3(B), dim3(64), stage, s, P, B, N, NX, NU, T, mode, soft, alphas, o, terms, x, u,
-                     dx, du, st, pcg_iters, tr, active_count, counters, hterms, qp_singular, activate, (int)stage);
+  hipLaunchKernelGGL(k_ls_decide, dim3(a.B), dim3(64), stage, s, a.P, a.B, a.N, a.NX, a.NU, a.T, a.mode, a.soft, a.alphas,
+                     a.o, a.terms, a.x, a.u, a.dx, a.du, a.st, a.pcg_iters, a.tr, a.active_count, a.counters, a.hterms,
+                     a.qp_singular, a.activate, (int)stage);
 }
 
 // The problems still alive in the lock-step loop (mask != 0), ascending, and their count: one
@@ -1625,16 +1606,10 @@ __global__ void __launch_bounds__(64) k_soft_outer(const ConstrDev* __restrict__
   }
 }
 
-void launch_soft_outer(hipStream_t s, const ConstrDev* Cs, PList P, int B, int N, int nj, double tol, int max_iter,
-                       double* x, double* u, double* mu, double* lam, double* phi, int* outer_active,
-                       int* outer_iter, int* exit_soft, int* outer_count, const ProbState* st, int* act_init,
-                       double rho_init, const StreamDev* sd, double* xs, const TraceDev* tr, double* lam_warm) {
-  ProbState none{};
-  StreamDev nosd{};
-  TraceDev notr{};
-  hipLaunchKernelGGL(k_soft_outer, dim3(B), dim3(64), 0, s, Cs, P, B, N, nj, tol, max_iter, x, u, mu, lam, phi,
-                     outer_active, outer_iter, exit_soft, outer_count, st ? *st : none, act_init, rho_init,
-                     sd ? *sd : nosd, xs, tr ? *tr : notr, lam_warm);
+void launch_soft_outer(hipStream_t s, const SoftOuterArgs& a) {
+  hipLaunchKernelGGL(k_soft_outer, dim3(a.B), dim3(64), 0, s, a.Cs, a.P, a.B, a.N, a.nj, a.tol, a.max_iter, a.x, a.u, a.mu,
+                     a.lam, a.phi, a.outer_active, a.outer_iter, a.exit_soft, a.outer_count, a.st, a.act_init, a.rho_init,
+                     a.sd, a.xs, a.tr, a.lam_warm);
 }
 
 // BoxConstraint.__init__ (:21-24): mu = mu_init, lambda = 0, phi = phi_init
@@ -1733,67 +1708,52 @@ __global__ void __launch_bounds__(256) k_goal_window(int B, int N, int nx, int R
   }
 }
 
-void launch_goal_window(hipStream_t s, int B, int N, int nx, int R, int M, int step, const double* xref,
-                        const int* pid, int pbase, const int* mask, double* gw) {
-  hipLaunchKernelGGL(k_goal_window, dim3(B), dim3(256), 0, s, B, N, nx, R, M, step, xref, pid, pbase, mask, gw);
+void launch_goal_window(hipStream_t s, const GoalWindowArgs& a) {
+  hipLaunchKernelGGL(k_goal_window, dim3(a.B), dim3(256), 0, s, a.B, a.N, a.nx, a.R, a.M, a.step, a.xref, a.pid, a.pbase,
+                     a.mask, a.gw);
 }
 
 
-int launch_qp_minv(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, PList P, int B, int N,
-                   const double* x, const int* need, double* minv) {
-  return dispatch_model(mid, nj, chain, [&](auto t) {
+int launch_qp_minv(bool f32, hipStream_t s, const ModelSel& m, const DynArgs& a) {
+  return dispatch_model(m.mid, m.nj, m.chain, [&](auto t) {
     using T = decltype(t);
-    Launch<T::nj, T::chain, typename T::model>::qp_minv(f32, s, M, P, B, N, x, need, minv);
+    Launch<T::nj, T::chain, typename T::model>::qp_minv(f32, s, m.M, a);
   });
 }
-int launch_qp_grad(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, PList P, int B, int N,
-                   double dt, const double* x, const int* need, const double* qdd, const double* minv, double* A,
-                   double* Bm) {
-  return dispatch_model(mid, nj, chain, [&](auto t) {
+int launch_qp_grad(bool f32, hipStream_t s, const ModelSel& m, const DynArgs& a) {
+  return dispatch_model(m.mid, m.nj, m.chain, [&](auto t) {
     using T = decltype(t);
-    Launch<T::nj, T::chain, typename T::model>::qp_grad(f32, s, M, P, B, N, dt, x, need, qdd, minv, A, Bm);
+    Launch<T::nj, T::chain, typename T::model>::qp_grad(f32, s, m.M, a);
   });
 }
-int launch_unit_minv(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, int K, const double* x,
-                     double* minv) {
-  return dispatch_model(mid, nj, chain, [&](auto t) {
+int launch_unit_minv(bool f32, hipStream_t s, const ModelSel& m, const DynArgs& a) {
+  return dispatch_model(m.mid, m.nj, m.chain, [&](auto t) {
     using T = decltype(t);
-    Launch<T::nj, T::chain, typename T::model>::unit_minv(f32, s, M, K, x, minv);
+    Launch<T::nj, T::chain, typename T::model>::unit_minv(f32, s, m.M, a);
   });
 }
-int launch_unit_grad(bool f32, hipStream_t s, int nj, bool chain, int mid, const ModelDev* M, int K, double dt,
-                     const double* x, const double* qdd, const double* minv, double* A, double* Bm, double* dqdd) {
-  return dispatch_model(mid, nj, chain, [&](auto t) {
+int launch_unit_grad(bool f32, hipStream_t s, const ModelSel& m, const DynArgs& a) {
+  return dispatch_model(m.mid, m.nj, m.chain, [&](auto t) {
     using T = decltype(t);
-    Launch<T::nj, T::chain, typename T::model>::unit_grad(f32, s, M, K, dt, x, qdd, minv, A, Bm, dqdd);
+    Launch<T::nj, T::chain, typename T::model>::unit_grad(f32, s, m.M, a);
   });
 }
 int launch_ginv(hipStream_t s, int nj, const CostDev* C, PList P, int B, const double* rho, const int* active,
                 double* G) {
   return for_nj<1, NJMAX>(nj, [&](auto n) { LaunchNJ<decltype(n)::value>::ginv(s, C, P, B, rho, active, G); });
 }
-int launch_qp(hipStream_t s, int nj, const CostDev* C, PList P, int B, int N, double dt, int precond, int mode,
-              const double* x, const double* u,
-              const int* active, const double* G, const double* A, const double* Bm, const double* cvec, double tol,
-              int max_iter, int* iters, double* dx, double* du, double* lam, double* Sd, double* Sl, double* gam,
-              double* Pd, const double* jsoft, const double* guess, double* Sg, const double* gw) {
-  const int rows = N * 2 * nj;
+int launch_qp(hipStream_t s, int nj, const QpArgs& a) {
+  const int rows = a.N * 2 * nj;
   if (rows > QP_MAX_ROWS) return -1;
-  if (nj > NJ_FULL && (rows > 1024 || jsoft)) return -2;   // a wide model: no HBM-row instance, no soft limits
-  const bool gm = nj <= NJ_FULL && (rows > 1024 || (rows >= qp_gm_min_rows() && mode == QP_MODE_PCG));
-  if (gm && mode == QP_MODE_PCG && !Sg) return -4;
-  if (qp_lds_doubles(N, 2 * nj, nj, gm ? QP_MAX_ROWS : 1024) * sizeof(double) > 160 * 1024) return -3;
-  return for_nj<1, NJMAX>(nj, [&](auto n) {
-    LaunchNJ<decltype(n)::value>::qp(s, C, P, B, N, dt, precond, mode, x, u, active, G, A, Bm, cvec, tol, max_iter, iters,
-                                     dx, du, lam, Sd, Sl, gam, Pd, jsoft, guess, Sg, gw);
-  });
+  if (nj > NJ_FULL && (rows > 1024 || a.jsoft)) return -2;   // a wide model: no HBM-row instance, no soft limits
+  const bool gm = nj <= NJ_FULL && (rows > 1024 || (rows >= qp_gm_min_rows() && a.mode == QP_MODE_PCG));
+  if (gm && a.mode == QP_MODE_PCG && !a.Sg) return -4;
+  if (qp_lds_doubles(a.N, 2 * nj, nj, gm ? QP_MAX_ROWS : 1024) * sizeof(double) > 160 * 1024) return -3;
+  return for_nj<1, NJMAX>(nj, [&](auto n) { LaunchNJ<decltype(n)::value>::qp(s, a); });
 }
-int launch_ginv_soft(hipStream_t s, int nj, const CostDev* C, const ConstrDev* Cs, PList P, int B, int N,
-                     const double* rho, const int* active, const double* x, const double* u, const double* mu,
-                     const double* lam, double* Gk, double* jsoft) {
-  return for_nj<1, NJ_FULL>(nj, [&](auto n) {   // no soft limits on a wide model
-    LaunchNJ<decltype(n)::value>::ginv_soft(s, C, Cs, P, B, N, rho, active, x, u, mu, lam, Gk, jsoft);
-  });
+int launch_ginv_soft(hipStream_t s, int nj, const GinvSoftArgs& a) {
+  // no soft limits on a wide model
+  return for_nj<1, NJ_FULL>(nj, [&](auto n) { LaunchNJ<decltype(n)::value>::ginv_soft(s, a); });
 }
 
 }  // namespace tmpc

@@ -32,26 +32,21 @@ hipStream_t ctx_stream(const tmpc_ctx* ctx) { return ctx->stream; }
 // lock-step loop)
 
 // the dynamics of the problems that need fresh gradients: defects c_k, M^-1, then A_k, B_k (SQP's QP and iLQR)
-static int run_dynamics(tmpc_ctx* ctx, int N, double dt, const double* d_x, const double* d_u, const ProbState& st,
-                        const Work& w, PList P, int nb) {
-  const int nj = ctx->hmodel.n;
-  const bool chain = ctx->hmodel.chain != 0;
-  {
-    Timed t(ctx, "qp_fd");
-    LAUNCH_OK(launch_qp_fd(val32(ctx), ctx->stream, nj, chain, ctx->model_id, ctx->dmodel, P, nb, N, dt, d_x, d_u, w.xs, st.need_grad,
-                           w.qdd, w.cvec));
-  }
-  {
-    Timed t(ctx, "qp_minv");
-    LAUNCH_OK(launch_qp_minv(dyn32(ctx), ctx->stream, nj, chain, ctx->model_id, ctx->dmodel, P, nb, N, d_x, st.need_grad,
-                             w.minv));
-  }
-  {
-    Timed t(ctx, "qp_grad");
-    LAUNCH_OK(launch_qp_grad(dyn32(ctx), ctx->stream, nj, chain, ctx->model_id, ctx->dmodel, P, nb, N, dt, d_x, st.need_grad, w.qdd, w.minv,
-                             w.A, w.Bm));
-  }
+static int run_dynamics(tmpc_ctx* ctx, const Work& w, PList P, int nb) {
+  const ModelSel m = model_sel(ctx);
+  DynArgs a = w.dyn;
+  a.P = P; a.B = nb;
+  { Timed t(ctx, "qp_fd"); LAUNCH_OK(launch_qp_fd(val32(ctx), ctx->stream, m, a)); }
+  { Timed t(ctx, "qp_minv"); LAUNCH_OK(launch_qp_minv(dyn32(ctx), ctx->stream, m, a)); }
+  { Timed t(ctx, "qp_grad"); LAUNCH_OK(launch_qp_grad(dyn32(ctx), ctx->stream, m, a)); }
   return 0;
+}
+
+void bind_work(const tmpc_ctx* ctx, int N, double dt, const double* d_x, const double* d_u, const ProbState& st,
+               Work& w) {
+  w.dyn.N = w.qp.N = w.gs.N = N; w.dyn.dt = w.qp.dt = dt; w.dyn.x = w.qp.x = w.gs.x = d_x;
+  w.dyn.u = w.qp.u = w.gs.u = d_u; w.dyn.need = st.need_grad; w.qp.active = w.gs.active = st.active; w.gs.rho = st.rho;
+  w.qp.C = w.gs.C = ctx->dcost; w.gs.Cs = ctx->dlim;
 }
 
 // the banded QP's three phases: rows + layout + Schur band, the solve, dxu
@@ -65,61 +60,53 @@ int run_hard_qp(tmpc_ctx* ctx, int nj, HardArgs& h) {
   return 0;
 }
 
-int run_qp(tmpc_ctx* ctx, int B, int N, double dt, int precond, const double* d_x, const double* d_u,
-           const ProbState& st, Work& w, bool keep_blocks, PList P, int nb) {
-  const int nj = ctx->hmodel.n;
-  const bool soft = w.jsoft != nullptr;
-  const double* G = soft ? w.Gk : w.G;
-  if (int rc = run_dynamics(ctx, N, dt, d_x, d_u, st, w, P, nb)) return rc;
-  if (soft) {
+int run_qp(tmpc_ctx* ctx, int B, int precond, const ProbState& st, Work& w, bool keep_blocks, PList P, int nb) {
+  const int nj = ctx->hmodel.n, N = w.qp.N;
+  const bool soft = w.qp.jsoft != nullptr;
+  if (int rc = run_dynamics(ctx, w, P, nb)) return rc;
+  {
     Timed t(ctx, "ginv");
-    LAUNCH_OK(launch_ginv_soft(ctx->stream, nj, ctx->dcost, ctx->dlim, P, nb, N, st.rho, st.active, d_x, d_u, w.smu,
-                               w.slam, w.Gk, w.jsoft));
-  } else {
-    Timed t(ctx, "ginv");
-    LAUNCH_OK(launch_ginv(ctx->stream, nj, ctx->dcost, P, nb, st.rho, st.active, w.G));
+    GinvSoftArgs g = w.gs;
+    g.P = P; g.B = nb;
+    if (soft) LAUNCH_OK(launch_ginv_soft(ctx->stream, nj, g));
+    else LAUNCH_OK(launch_ginv(ctx->stream, nj, ctx->dcost, P, nb, st.rho, st.active, w.G));
   }
+  // what every phase of the fused QP reads; a phase adds its mode, the PCG's bounds and the outputs it writes
+  QpArgs q = w.qp;
+  q.P = P; q.B = nb; q.precond = PRECOND_SS; q.G = soft ? w.gs.Gk : w.G;
   if (w.hard) {   // hard box constraints: rows of C per knot, banded S (tmpc_hard.hip)
     HardArgs h = *w.hard;
-    h.precond = precond; h.Ghat = G; h.per_knot = soft || ctx->hcost.kind == COST_EE; h.A = w.A; h.Bm = w.Bm;
-    h.cvec = w.cvec; h.jsoft = w.jsoft; h.x = d_x; h.u = d_u; h.active = st.active; h.iters = w.iters;
-    h.dx = w.dx; h.du = w.du; h.tol = ctx->opts.exit_tolerance_linSys; h.max_iter = ctx->opts.max_iter_linSys;
+    h.precond = precond; h.Ghat = q.G; h.per_knot = soft || ctx->hcost.kind == COST_EE; h.A = q.A; h.Bm = q.Bm;
+    h.cvec = q.cvec; h.jsoft = q.jsoft; h.x = q.x; h.u = q.u; h.active = st.active; h.iters = q.iters;
+    h.dx = q.dx; h.du = q.du; h.tol = ctx->opts.exit_tolerance_linSys; h.max_iter = ctx->opts.max_iter_linSys;
     h.iter = st.iter; h.Wtr = w.Wtr; h.tr_active = w.tr_active;
-    HIP_OK(hipMemsetAsync(w.iters, 0, sizeof(int) * B, ctx->stream));
-    if (w.gw) {   // tracking: the cost gradient against the goal window, as the banded kernels' gvec input
+    HIP_OK(hipMemsetAsync(q.iters, 0, sizeof(int) * B, ctx->stream));
+    if (q.gw) {   // tracking: the cost gradient against the goal window, as the banded kernels' gvec input
       BUF(double, hd_gvec, (size_t)B * N * 3 * nj);
       Timed t(ctx, "hard_track_grad");
-      LAUNCH_OK(launch_hard_track_grad(ctx->stream, nj, h, w.gw, hd_gvec));
+      LAUNCH_OK(launch_hard_track_grad(ctx->stream, nj, h, q.gw, hd_gvec));
       h.gvec = hd_gvec;
     }
     return run_hard_qp(ctx, nj, h);
   }
   if (precond == 0) {   // method S: Schur blocks -> direct solve -> dxu
-    {
-      Timed t(ctx, "schur");
-      LAUNCH_OK(launch_qp(ctx->stream, nj, ctx->dcost, P, nb, N, dt, PRECOND_SS, QP_MODE_SCHUR, d_x, d_u, st.active, G,
-                          w.A, w.Bm, w.cvec, 0.0, 0, w.iters, w.dx, w.du, nullptr, w.Sd, w.Sl, w.gam, nullptr,
-                          w.jsoft, nullptr, nullptr, w.gw));
-    }
-    {
-      Timed t(ctx, "btsolve");
-      LAUNCH_OK(launch_btsolve(ctx->stream, 2 * nj, B, N, st.active, w.Sd, w.Sl, w.gam, w.U, w.Y, w.lam));
-    }
-    {
-      Timed t(ctx, "dxu");
-      LAUNCH_OK(launch_qp(ctx->stream, nj, ctx->dcost, P, nb, N, dt, PRECOND_SS, QP_MODE_DXU, d_x, d_u, st.active, G, w.A,
-                          w.Bm, w.cvec, 0.0, 0, w.iters, w.dx, w.du, w.lam, nullptr, nullptr, nullptr, nullptr,
-                          w.jsoft, nullptr, nullptr, w.gw));
-    }
+    QpArgs a = q;
+    a.mode = QP_MODE_SCHUR; a.Sd = w.Sd; a.Sl = w.Sl; a.gam = w.gam;
+    { Timed t(ctx, "schur"); LAUNCH_OK(launch_qp(ctx->stream, nj, a)); }
+    a.P = PList{}; a.B = B; a.U = w.U; a.Y = w.Y; a.lam = w.lam;   // every problem: k_btsolve takes no problem list
+    { Timed t(ctx, "btsolve"); LAUNCH_OK(launch_btsolve(ctx->stream, 2 * nj, a)); }
+    a = q;
+    a.mode = QP_MODE_DXU; a.lam = w.lam;
+    { Timed t(ctx, "dxu"); LAUNCH_OK(launch_qp(ctx->stream, nj, a)); }
     return 0;
   }
   {
+    QpArgs a = q;
+    a.mode = QP_MODE_PCG; a.precond = precond; a.tol = ctx->opts.exit_tolerance_linSys;
+    a.max_iter = ctx->opts.max_iter_linSys; a.guess = w.guess; a.Sg = w.Sg; a.lam = keep_blocks ? w.lam : w.lam_keep;
+    if (keep_blocks) { a.Sd = w.Sd; a.Sl = w.Sl; a.gam = w.gam; a.Pd = w.Pd; }
     Timed t(ctx, "qp");
-    LAUNCH_OK(launch_qp(ctx->stream, nj, ctx->dcost, P, nb, N, dt, precond, QP_MODE_PCG, d_x, d_u, st.active, G, w.A,
-                        w.Bm, w.cvec, ctx->opts.exit_tolerance_linSys, ctx->opts.max_iter_linSys, w.iters, w.dx,
-                        w.du, keep_blocks ? w.lam : w.lam_keep, keep_blocks ? w.Sd : nullptr,
-                        keep_blocks ? w.Sl : nullptr, keep_blocks ? w.gam : nullptr, keep_blocks ? w.Pd : nullptr,
-                        w.jsoft, w.guess, w.Sg, w.gw));
+    LAUNCH_OK(launch_qp(ctx->stream, nj, a));
   }
   return 0;
 }
@@ -138,8 +125,8 @@ int alloc_work(tmpc_ctx* ctx, int B, int N, Work& w, bool with_blocks) {
   BUF(int, iters, (size_t)B);
   ctx->qp_last = {0, 0, 0, -1, false, false};   // these buffers are about to be rewritten (tmpc_qp_last_inputs)
   w = Work{};   // everything else null until its user sets it
-  w.xs = xs; w.qdd = qdd; w.minv = minv; w.cvec = cvec; w.A = Amat; w.Bm = Bmat; w.G = Ginv;
-  w.dx = dx; w.du = du; w.iters = iters;
+  w.dyn.xs = w.xs = xs; w.dyn.qdd = qdd; w.dyn.minv = minv; w.qp.cvec = w.dyn.cvec = cvec; w.qp.A = w.dyn.A = Amat;
+  w.qp.Bm = w.dyn.Bm = Bmat; w.G = Ginv; w.qp.dx = dx; w.qp.du = du; w.qp.iters = iters;
   if (N * nx >= qp_gm_min_rows() && !qp_banded(ctx, N)) {   // the GM QP kernel's rows of S / P^-1
     BUF(double, qp_gm, qp_gm_doubles(B, N, nx));
     w.Sg = qp_gm;
@@ -164,7 +151,7 @@ int alloc_work(tmpc_ctx* ctx, int B, int N, Work& w, bool with_blocks) {
 }
 
 int goal_window(tmpc_ctx* ctx, int B, int N, int rows, const char* rows_name, const int* pid, int pbase,
-                const int* mask, double** gw) {
+                const int* mask, const double** gw) {
   *gw = nullptr;
   if (!ctx->ref_R) return 0;
   if (ctx->hcost.kind == COST_EE)
@@ -174,8 +161,10 @@ int goal_window(tmpc_ctx* ctx, int B, int N, int rows, const char* rows_name, co
     return fail(ctx, "reference rows R = %d: must be 1 or the %s (%d)", ctx->ref_R, rows_name, rows);
   const int nx = 2 * ctx->hmodel.n;
   BUF(double, goal_win, (size_t)B * N * nx);
-  launch_goal_window(ctx->stream, B, N, nx, ctx->ref_R, ctx->ref_M, ctx->ref_step, ctx->ref_dev, pid, pbase, mask,
-                     goal_win);
+  GoalWindowArgs a{};
+  a.B = B; a.N = N; a.nx = nx; a.R = ctx->ref_R; a.M = ctx->ref_M; a.step = ctx->ref_step; a.xref = ctx->ref_dev;
+  a.pid = pid; a.pbase = pbase; a.mask = mask; a.gw = goal_win;
+  launch_goal_window(ctx->stream, a);
   HIP_OK(hipGetLastError());
   *gw = goal_win;
   return 0;
@@ -244,10 +233,11 @@ int init_soft(tmpc_ctx* ctx, int B, int N, bool fresh, Work* w) {
   if (w) {
     BUF(double, soft_Gk, (size_t)B * N * (nx * nx + nj * nj));
     BUF(double, soft_j, (size_t)B * N * (nx + nj));
-    w->Gk = soft_Gk;
-    w->jsoft = soft_j;
-    w->smu = ctx->soft_mu;
-    w->slam = ctx->soft_lam;
+    w->gs.Gk = soft_Gk;
+    w->gs.jsoft = soft_j;
+    w->qp.jsoft = soft_j;
+    w->gs.mu = ctx->soft_mu;
+    w->gs.lam = ctx->soft_lam;
   }
   return 0;
 }
@@ -405,7 +395,7 @@ static int lockstep_loop(tmpc_ctx* ctx, long cap, int* active_count, AliveList& 
   hipEvent_t ev[2] = {get_event(ctx), get_event(ctx)};
   if (!ev[0] || !ev[1]) return fail(ctx, "hipEventCreate failed");
   int rc = 0;
-  launch_alive_list(ctx->stream, al.B, al.mask, al.idx, al.cnt, nullptr);
+  launch_alive_list(ctx->stream, al.B, al.mask, al.idx, al.cnt);
   HIP_OK(hipGetLastError());
   al.P = PList{al.idx, al.cnt};
   al.nb = al.B;
@@ -446,13 +436,13 @@ struct Outer {
   TraceDev tr;
   int* active_count;   // [2][4] (lag-1 double buffer): [0] some problem in its inner loop, [1] some problem restarted a pass, [2] problem-list length
   unsigned long long* counters;
-  int *outer_active, *outer_iter, *exit_soft;
+  SoftOuterArgs so;   // the outer loop's block: its state (outer_alloc) and the soft state the solver runs on (mu, lam,
+                      // phi: its caller sets them; null: none); outer_run adds the rest
   bool soft;          // soft box limits
   bool per_problem;   // the outer loop per problem (k_soft_outer with act_init): soft limits, and every stream (a slot's
                       // problem is finished when it leaves its outer loop, which without soft limits is
                       // check_and_update's exit 1)
   AliveList alv;
-  double *smu, *slam, *sphi;   // the soft state the solver runs on (its caller sets them; null: none)
 };
 
 // Allocation only, but for alloc_trace's memset: nothing else goes onto the stream here.
@@ -468,9 +458,9 @@ static int outer_alloc(tmpc_ctx* ctx, int B, int N, bool with_blocks, bool strea
   BUF(int, exit_soft, B);
   o.active_count = active_count;
   o.counters = counters;
-  o.outer_active = outer_active;
-  o.outer_iter = ctx->outer_iter = outer_iter;
-  o.exit_soft = ctx->exit_soft = exit_soft;
+  o.so.outer_active = outer_active;
+  o.so.outer_iter = ctx->outer_iter = outer_iter;
+  o.so.exit_soft = ctx->exit_soft = exit_soft;
   o.soft = ctx->hlim.any != 0;
   o.per_problem = o.soft || stream;
   return alloc_alive(ctx, B, o.per_problem ? outer_active : o.st.active, o.alv);
@@ -498,18 +488,20 @@ static int outer_run(tmpc_ctx* ctx, int B, int N, Outer& o, double* d_x, double*
   // xs = x[:, 0] (:527)
   HIP_OK(hipMemcpy2DAsync(o.w.xs, sizeof(double), d_x, (size_t)N * sizeof(double), sizeof(double), (size_t)B * nx,
                           hipMemcpyDeviceToDevice, ctx->stream));
-  launch_outer_init(ctx->stream, B, o.outer_active, o.outer_iter, o.exit_soft);
-  launch_init_state(ctx->stream, B, op.rho_init_SQP_DDP, o.st, o.outer_active);
+  launch_outer_init(ctx->stream, B, o.so.outer_active, o.so.outer_iter, o.so.exit_soft);
+  launch_init_state(ctx->stream, B, op.rho_init_SQP_DDP, o.st, o.so.outer_active);
   HIP_OK(hipMemsetAsync(o.active_count, 0, 8 * sizeof(int), ctx->stream));
   if ((rc = init(o.st.active, o.active_count, nullptr))) return rc;
+  SoftOuterArgs& sa = o.so;   // check_and_update_soft_constraints; a launch adds its problems and its flag slot
+  sa.Cs = ctx->dlim; sa.N = N; sa.nj = nj; sa.tol = op.exit_tolerance_softConstraints;
+  sa.max_iter = op.max_iter_softConstraints; sa.x = d_x; sa.u = d_u;
   if (!o.per_problem) {
     // one inner loop (at most max_iter iterations, + 1 for the lag of the exit test);
     // check_and_update_soft_constraints then exits 1 (:531-757)
     rc = lockstep_loop(ctx, (long)op.max_iter_SQP_DDP + 1, o.active_count, o.alv, iteration);
     if (rc) return rc;
-    launch_soft_outer(ctx->stream, ctx->dlim, PList{nullptr, nullptr}, B, N, nj, op.exit_tolerance_softConstraints,
-                      op.max_iter_softConstraints, d_x, d_u, o.smu, o.slam, o.sphi, o.outer_active, o.outer_iter,
-                      o.exit_soft, o.active_count);
+    sa.B = B; sa.outer_count = o.active_count;
+    launch_soft_outer(ctx->stream, sa);
     HIP_OK(hipGetLastError());
   } else {
     BUF(int, act_init, B);
@@ -517,20 +509,23 @@ static int outer_run(tmpc_ctx* ctx, int B, int N, Outer& o, double* d_x, double*
     const long per = (long)(op.max_iter_softConstraints + 1) * (op.max_iter_SQP_DDP + 1) + 3;
     // a stream: every batch iteration advances some problem by one iteration, so P x per bounds it
     const long cap = sd ? per * sd->P + 3 : per;
+    // the outer loop per problem, and a stream's hand-over of finished slots
+    sa.st = o.st; sa.act_init = act_init; sa.rho_init = op.rho_init_SQP_DDP; sa.xs = o.w.xs; sa.tr = o.tr;
+    sa.lam_warm = lam_keep;
+    if (sd) sa.sd = *sd;
     rc = lockstep_loop(ctx, cap, o.active_count, o.alv, [&](int* ac) -> int {
       int r = iteration(ac);
       if (r) return r;
       {   // a stream: k_soft_outer also hands finished slots on (finished problems out, pending ones in)
         Timed t(ctx, "soft_outer");
-        launch_soft_outer(ctx->stream, ctx->dlim, o.alv.P, o.alv.nb, N, nj, op.exit_tolerance_softConstraints,
-                          op.max_iter_softConstraints, d_x, d_u, o.smu, o.slam, o.sphi, o.outer_active, o.outer_iter,
-                          o.exit_soft, ac + 1, &o.st, act_init, op.rho_init_SQP_DDP, sd, o.w.xs, &o.tr, lam_keep);
+        sa.P = o.alv.P; sa.B = o.alv.nb; sa.outer_count = ac + 1;
+        launch_soft_outer(ctx->stream, sa);
         HIP_OK(hipGetLastError());
-        if (sd && o.w.gw) {   // tracking: the goals of the problems that just entered a slot (act_init)
-          launch_goal_window(ctx->stream, B, N, nx, ctx->ref_R, ctx->ref_M, 0, ctx->ref_dev, sd->slot_pid, sd->pbase,
-                             act_init, o.w.gw);
-          HIP_OK(hipGetLastError());
-        }
+        // tracking: the goals of the problems that just entered a slot (act_init), into the solve's window (a
+        // stream runs outside the MPC loop, so ctx->ref_step is 0: the reference's first column)
+        if (sd && o.w.qp.gw && (r = goal_window(ctx, B, N, sd->period, "stream's period", sd->slot_pid, sd->pbase,
+                                                act_init, &o.w.qp.gw)))
+          return r;
       }
       // restarted passes (act_init, set by k_soft_outer) and a stream's new problems: initial cost / merit, then
       // into the inner loop; masked by act_init, so a no-op when no pass restarted
@@ -546,7 +541,7 @@ static int outer_run(tmpc_ctx* ctx, int B, int N, Outer& o, double* d_x, double*
   for (int i = 0; i < 3; ++i) ctx->last_counters[i] = (int64_t)hc[i];
   ctx->last_counters[3] = (int64_t)T;
   if (o.w.hard && (rc = collect_hard_work(ctx, *o.w.hard))) return rc;
-  if (sd && o.smu) ctx->soft_B = ctx->soft_N = -1;   // the slots' constants are no caller's state
+  if (sd && o.so.mu) ctx->soft_B = ctx->soft_N = -1;   // the slots' constants are no caller's state
   resolve_timings(ctx);
   return 0;
 }
@@ -563,9 +558,8 @@ int sqp_device(tmpc_ctx* ctx, int B, int N, double dt, int linsys, double* d_x, 
   if (precond < 0)
     return fail(ctx, "linear system method %d is not available on the GPU (use S/PCG-J/BJ/SS = 1/2/3/4)", linsys);
   const int nj = ctx->hmodel.n, nx = 2 * nj;
-  const bool chain = ctx->hmodel.chain != 0;
+  const ModelSel m = model_sel(ctx);
   const tmpc_options& o = ctx->opts;
-  const SolverOpts so = solver_opts(o);
   const std::vector<double> al = alpha_list(o);
   const int T = (int)al.size();
   const int W = o.max_iter_SQP_DDP + 1;
@@ -582,9 +576,7 @@ int sqp_device(tmpc_ctx* ctx, int B, int N, double dt, int linsys, double* d_x, 
   const bool perknot = soft || ctx->hcost.kind == COST_EE;
   if (perknot) {   // a stream's problems start from the initial constants
     if ((rc = init_soft(ctx, B, N, sd != nullptr, &w))) return rc;
-    L.smu = ctx->soft_mu;
-    L.slam = ctx->soft_lam;
-    L.sphi = ctx->soft_phi;
+    L.so.mu = ctx->soft_mu; L.so.lam = ctx->soft_lam; L.so.phi = ctx->soft_phi;
   }
   // hard box constraints (ACTIVE_SET / FULL_SET): per-knot rows, a banded Schur complement per problem
   HardArgs hard{};
@@ -627,34 +619,46 @@ int sqp_device(tmpc_ctx* ctx, int B, int N, double dt, int linsys, double* d_x, 
   }
   // the goals of a tracking solve (a stream: of the problems now in the slots)
   if ((rc = goal_window(ctx, B, N, sd ? sd->period : B, sd ? "stream's period" : "batch size",
-                        sd ? sd->slot_pid : nullptr, sd ? sd->pbase : 0, nullptr, &w.gw)))
+                        sd ? sd->slot_pid : nullptr, sd ? sd->pbase : 0, nullptr, &w.qp.gw)))
     return rc;
+  bind_work(ctx, N, dt, d_x, d_u, st, w);
+  // the line search's two launches: what the initial merit and an iteration's trials share
+  LsTermsArgs lt{};
+  lt.C = ctx->dcost; lt.Cs = ctx->dlim; lt.mu = L.so.mu; lt.lam = L.so.lam; lt.N = N; lt.dt = dt; lt.x = d_x; lt.u = d_u;
+  lt.xs = w.xs; lt.terms = terms; lt.gw = w.qp.gw;
+  DecideArgs ld{};
+  ld.N = N; ld.NX = nx; ld.NU = nj; ld.soft = soft; ld.o = solver_opts(o); ld.terms = terms; ld.x = d_x; ld.u = d_u;
+  ld.dx = w.qp.dx; ld.du = w.qp.du; ld.st = st; ld.tr = L.tr; ld.hterms = hterms;
   // initial J, c, merit (:541-548)
   auto init_merit = [&](int* mask, int* ac, int* activate) -> int {
-    ProbState sti = st;
-    sti.active = mask;
-    LAUNCH_OK(launch_ls_terms(val32(ctx), ctx->stream, nj, chain, ctx->model_id, ctx->dmodel, ctx->dcost, ctx->dlim, L.smu, L.slam,
-                              alv.P, alv.nb, N, 1, dt, alphas + T, d_x, d_u, w.xs, nullptr, nullptr, mask, terms,
-                              w.gw));
+    LsTermsArgs a = lt;
+    a.P = alv.P; a.B = alv.nb; a.T = 1; a.alphas = alphas + T; a.active = mask;
+    LAUNCH_OK(launch_ls_terms(val32(ctx), ctx->stream, m, a));
     if (hterms) LAUNCH_OK(hard_ls(ctx, nj, hard, B, N, 1, alphas + T, d_x, d_u, nullptr, nullptr, mask));
-    launch_ls_decide(ctx->stream, alv.P, alv.nb, N, nx, nj, 1, LS_MODE_INIT, soft, alphas + T, so, terms, d_x, d_u, w.dx, w.du,
-                     sti, nullptr, L.tr, ac, nullptr, hterms, nullptr, activate);
+    DecideArgs d = ld;
+    d.P = alv.P; d.B = alv.nb; d.T = 1; d.mode = LS_MODE_INIT; d.alphas = alphas + T; d.st.active = mask;
+    d.active_count = ac; d.activate = activate;
+    launch_ls_decide(ctx->stream, d);
     HIP_OK(hipGetLastError());
     return 0;
   };
   // one SQP iteration (:550-757)
   auto sqp_iteration = [&](int* ac) -> int {
-    int rc2 = run_qp(ctx, B, N, dt, precond, d_x, d_u, st, w, false, alv.P, alv.nb);
+    int rc2 = run_qp(ctx, B, precond, st, w, false, alv.P, alv.nb);
     if (rc2) return rc2;
     {
+      LsTermsArgs a = lt;
+      a.P = alv.P; a.B = alv.nb; a.T = T; a.alphas = alphas; a.dx = w.qp.dx; a.du = w.qp.du; a.active = st.active;
       Timed t(ctx, "ls_terms");
-      LAUNCH_OK(launch_ls_terms(val32(ctx), ctx->stream, nj, chain, ctx->model_id, ctx->dmodel, ctx->dcost, ctx->dlim, L.smu, L.slam,
-                                alv.P, alv.nb, N, T, dt, alphas, d_x, d_u, w.xs, w.dx, w.du, st.active, terms, w.gw));
-      if (hterms) LAUNCH_OK(hard_ls(ctx, nj, hard, B, N, T, alphas, d_x, d_u, w.dx, w.du, st.active));
+      LAUNCH_OK(launch_ls_terms(val32(ctx), ctx->stream, m, a));
+      if (hterms) LAUNCH_OK(hard_ls(ctx, nj, hard, B, N, T, alphas, d_x, d_u, w.qp.dx, w.qp.du, st.active));
     }
+    DecideArgs d = ld;
+    d.P = alv.P; d.B = alv.nb; d.T = T; d.mode = LS_MODE_STEP; d.alphas = alphas; d.pcg_iters = w.qp.iters;
+    d.active_count = ac; d.counters = prob_counters;
+    if (w.hard && precond == 0) d.qp_singular = hard.sing;
     Timed t(ctx, "ls_decide");
-    launch_ls_decide(ctx->stream, alv.P, alv.nb, N, nx, nj, T, LS_MODE_STEP, soft, alphas, so, terms, d_x, d_u, w.dx, w.du,
-                     st, w.iters, L.tr, ac, prob_counters, hterms, (w.hard && precond == 0) ? hard.sing : nullptr);
+    launch_ls_decide(ctx->stream, d);
     HIP_OK(hipGetLastError());
     return 0;
   };
@@ -682,36 +686,27 @@ int ilqr_sweep_setup(tmpc_ctx* ctx, int B, int N, bool fresh_soft, IlqrSweep& q)
   BUF(double, il_ut, (size_t)B * T * nj * K);
   BUF(double, il_J, (size_t)B * T);
   q = IlqrSweep{};
+  q.C = ctx->dcost; q.Cs = ctx->dlim; q.N = N;
   q.T = T; q.alphas = alphas; q.K = il_K; q.d = il_d; q.dV = il_dV; q.ok = il_ok; q.xt = il_xt; q.ut = il_ut;
-  q.J = il_J;
+  q.Jt = il_J;
   if (ctx->hlim.any) {
     if ((rc = init_soft(ctx, B, N, fresh_soft, nullptr))) return rc;
-    q.smu = ctx->soft_mu;
-    q.slam = ctx->soft_lam;
-    q.sphi = ctx->soft_phi;
+    q.mu = ctx->soft_mu;
+    q.lam = ctx->soft_lam;
     BUF(double, il_jac_buf, (size_t)B * N * 3 * nj);   // soft-limit jacobians of every knot (Riccati sweep)
-    q.jac = il_jac_buf;
+    q.jscratch = il_jac_buf;
   }
   HIP_OK(hipMemcpyAsync(alphas, al.data(), al.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   return 0;
 }
 
-int ilqr_sweeps(tmpc_ctx* ctx, int N, double dt, const double* d_x, const double* d_u, const ProbState& st,
-                const Work& w, PList P, int nb, const IlqrSweep& q) {
-  const int nj = ctx->hmodel.n;
-  const bool chain = ctx->hmodel.chain != 0;
-  if (int r = run_dynamics(ctx, N, dt, d_x, d_u, st, w, P, nb)) return r;
-  {
-    Timed t(ctx, "ilqr_backward");
-    LAUNCH_OK(launch_ilqr_backward(ric32(ctx), ctx->stream, nj, ctx->dcost, ctx->dlim, P, nb, N, d_x, d_u, st.rho,
-                                   st.active, w.A, w.Bm, q.smu, q.slam, q.jac, q.K, q.d, q.dV, q.ok, w.gw));
-  }
-  {
-    Timed t(ctx, "ilqr_forward");
-    LAUNCH_OK(launch_ilqr_forward(val32(ctx), ctx->stream, nj, chain, ctx->model_id, ctx->dmodel, ctx->dcost, ctx->dlim,
-                                  q.smu, q.slam, P, nb, N, q.T, dt, 0, q.alphas, d_x, d_u, q.K, q.d, st.active, q.ok,
-                                  q.xt, q.ut, q.J, w.gw));
-  }
+int ilqr_sweeps(tmpc_ctx* ctx, const ProbState& st, const Work& w, PList P, int nb, const IlqrSweep& q) {
+  if (int r = run_dynamics(ctx, w, P, nb)) return r;
+  IlqrArgs a = q;   // the trajectory and the blocks the dynamics just wrote: as run_dynamics' (bind_work)
+  a.P = P; a.B = nb; a.N = w.dyn.N; a.dt = w.dyn.dt; a.x = w.dyn.x; a.u = w.dyn.u; a.rho = st.rho; a.active = st.active;
+  a.A = w.dyn.A; a.Bm = w.dyn.Bm; a.gw = w.qp.gw;
+  { Timed t(ctx, "ilqr_backward"); LAUNCH_OK(launch_ilqr_backward(ric32(ctx), ctx->stream, ctx->hmodel.n, a)); }
+  { Timed t(ctx, "ilqr_forward"); LAUNCH_OK(launch_ilqr_forward(val32(ctx), ctx->stream, model_sel(ctx), a)); }
   return 0;
 }
 
@@ -721,9 +716,7 @@ int ilqr_device(tmpc_ctx* ctx, int B, int N, double dt, double* d_x, double* d_u
   int rc = ilqr_sweep_setup(ctx, B, N, sd != nullptr, q);   // a stream's problems start from the initial constants
   if (rc) return rc;
   const int nj = ctx->hmodel.n, nx = 2 * nj;
-  const bool chain = ctx->hmodel.chain != 0;
-  const tmpc_options& o = ctx->opts;
-  const SolverOpts so = solver_opts(o);
+  const ModelSel m = model_sel(ctx);
   const int T = q.T;
   Outer L{};
   if ((rc = outer_alloc(ctx, B, N, false, sd != nullptr, L))) return rc;
@@ -733,9 +726,9 @@ int ilqr_device(tmpc_ctx* ctx, int B, int N, double dt, double* d_x, double* d_u
   BUF(unsigned long long, il_prob_counters, (size_t)B * 3);   // per-problem tallies of k_ilqr_decide
   HIP_OK(hipMemsetAsync(L.counters, 0, 4 * sizeof(unsigned long long), ctx->stream));
   HIP_OK(hipMemsetAsync(il_prob_counters, 0, (size_t)B * 3 * sizeof(unsigned long long), ctx->stream));
-  L.smu = q.smu;
-  L.slam = q.slam;
-  L.sphi = q.sphi;
+  if (q.mu) {   // the soft state the sweeps run on (ilqr_sweep_setup): the outer loop updates it
+    L.so.mu = ctx->soft_mu; L.so.lam = ctx->soft_lam; L.so.phi = ctx->soft_phi;
+  }
   StreamDev sdr{};
   if (sd) {
     // a stream's problems start from the rollout of u from x[:, 0] too: roll the `period` inputs out once
@@ -745,35 +738,40 @@ int ilqr_device(tmpc_ctx* ctx, int B, int N, double dt, double* d_x, double* d_u
     BUF(double, stream_xr, (size_t)sd->period * nx * N);
     HIP_OK(hipMemcpyAsync(stream_xr, sd->x_in, (size_t)sd->period * nx * N * sizeof(double), hipMemcpyDeviceToDevice,
                           ctx->stream));
-    LAUNCH_OK(launch_rollout(val32(ctx), ctx->stream, nj, chain, ctx->model_id, ctx->dmodel, sd->period, N, dt,
-                             stream_xr, sd->u_in));
+    LAUNCH_OK(launch_rollout(val32(ctx), ctx->stream, m, Batch{{}, sd->period, N}, dt, stream_xr, sd->u_in));
     sdr.x_in = stream_xr;
     launch_stream_init(ctx->stream, B, sdr, d_x, d_u);   // slot s starts with problem s
     HIP_OK(hipGetLastError());
   } else {
     // iLQR iterates are rollouts: start from the rollout of u from x[:, 0]
-    LAUNCH_OK(launch_rollout(val32(ctx), ctx->stream, nj, chain, ctx->model_id, ctx->dmodel, B, N, dt, d_x, d_u));
+    LAUNCH_OK(launch_rollout(val32(ctx), ctx->stream, m, Batch{{}, B, N}, dt, d_x, d_u));
   }
   // the goals of a tracking solve (a stream: of the problems now in the slots)
   if ((rc = goal_window(ctx, B, N, sd ? sd->period : B, sd ? "stream's period" : "batch size",
-                        sd ? sd->slot_pid : nullptr, sd ? sd->pbase : 0, nullptr, &w.gw)))
+                        sd ? sd->slot_pid : nullptr, sd ? sd->pbase : 0, nullptr, &w.qp.gw)))
     return rc;
+  bind_work(ctx, N, dt, d_x, d_u, st, w);
+  // the decision's block: what the initial cost and an iteration share
+  DecideArgs dc{};
+  dc.N = N; dc.NX = nx; dc.NU = nj; dc.alphas = q.alphas; dc.o = solver_opts(ctx->opts); dc.Jt = q.Jt; dc.dV = q.dV;
+  dc.ok = q.ok; dc.xt = q.xt; dc.ut = q.ut; dc.x = d_x; dc.u = d_u; dc.st = st; dc.tr = L.tr;
   // J at the current trajectory
   auto init_cost = [&](int* mask, int* ac, int* activate) -> int {
-    ProbState sti = st;
-    sti.active = mask;
-    LAUNCH_OK(launch_ilqr_init_cost(ctx->stream, nj, ctx->dcost, ctx->dlim, L.smu, L.slam, alv.P, alv.nb, N, d_x, d_u,
-                                    mask, q.J, w.gw));
-    launch_ilqr_decide(ctx->stream, alv.P, alv.nb, N, nx, nj, 1, 1, q.alphas, so, q.J, q.dV, q.ok, q.xt, q.ut, d_x, d_u,
-                       sti, L.tr, ac, nullptr, activate);
+    IlqrArgs a = q;
+    a.P = alv.P; a.B = alv.nb; a.x = d_x; a.u = d_u; a.active = mask; a.gw = w.qp.gw;
+    LAUNCH_OK(launch_ilqr_init_cost(ctx->stream, nj, a));
+    DecideArgs d = dc;
+    d.P = alv.P; d.B = alv.nb; d.T = 1; d.init = 1; d.st.active = mask; d.active_count = ac; d.activate = activate;
+    launch_ilqr_decide(ctx->stream, d);
     HIP_OK(hipGetLastError());
     return 0;
   };
   auto ilqr_iteration = [&](int* ac) -> int {
-    if (int r = ilqr_sweeps(ctx, N, dt, d_x, d_u, st, w, alv.P, alv.nb, q)) return r;
+    if (int r = ilqr_sweeps(ctx, st, w, alv.P, alv.nb, q)) return r;
+    DecideArgs d = dc;
+    d.P = alv.P; d.B = alv.nb; d.T = T; d.active_count = ac; d.counters = il_prob_counters;
     Timed t(ctx, "ilqr_decide");
-    launch_ilqr_decide(ctx->stream, alv.P, alv.nb, N, nx, nj, T, 0, q.alphas, so, q.J, q.dV, q.ok, q.xt, q.ut, d_x, d_u,
-                       st, L.tr, ac, il_prob_counters);
+    launch_ilqr_decide(ctx->stream, d);
     HIP_OK(hipGetLastError());
     return 0;
   };
@@ -924,7 +922,6 @@ int mpc_device(tmpc_ctx* ctx, int B, int N, double dt, int solver, int steps, do
     return fail(ctx, "pcg_warm_start with hard box constraints or past the fused QP's rows: the banded PCG takes "
                 "no guess; unset pcg_warm_start");
   const int nj = ctx->hmodel.n, nx = 2 * nj;
-  const bool chain = ctx->hmodel.chain != 0;
   // work counters of the whole loop: the sum over its horizon solves (tmpc_solve_counters)
   int64_t sum_counters[3] = {0, 0, 0};
   // executed state 0 = x[:, 0]
@@ -952,8 +949,9 @@ int mpc_device(tmpc_ctx* ctx, int B, int N, double dt, int solver, int steps, do
                             sizeof(int), B, hipMemcpyDeviceToDevice, ctx->stream));
     {
       Timed t(ctx, "mpc_shift");
-      LAUNCH_OK(launch_mpc_shift(ctx->stream, nj, chain, ctx->model_id, ctx->dmodel, B, N, dt, s, steps, d_x, d_u,
-                                 d_xe, d_ue));
+      ShiftArgs a{};
+      a.B = B; a.N = N; a.dt = dt; a.step = s; a.steps = steps; a.x = d_x; a.u = d_u; a.xe = d_xe; a.ue = d_ue;
+      LAUNCH_OK(launch_mpc_shift(ctx->stream, model_sel(ctx), a));
     }
     // QuadraticCost.shift_QF_start(-1) (TrajoptCost.py:100-104)
     if (ctx->hcost.QF_start >= 0) {
