@@ -38,7 +38,7 @@ dynamically feasible, so the constraint violation c is 0 throughout).
 """
 import numpy as np
 
-from . import rbd
+from . import rbd, state
 from .sqp import default_options, total_cost
 
 
@@ -230,11 +230,9 @@ def step(model, cost, x, u, N, dt, rho, J, o, soft=None, solve="canonical"):
     while True:
         xn, un = forward(model, x, u, K, d, alpha, dt)
         J_new = total_cost(cost, xn, un, N, soft)
-        delta_J = J - J_new
-        with np.errstate(divide="ignore", invalid="ignore"):
-            ratio = np.float64(delta_J) / np.float64(-alpha * (dV1 + alpha * dV2))
+        delta_J, ratio, accepted = state.ilqr_trial(o, J, J_new, dV1, dV2, alpha)
         trials.append((alpha, J_new, ratio))
-        if ratio >= o["expected_reduction_min_SQP_DDP"] and ratio <= o["expected_reduction_max_SQP_DDP"]:
+        if accepted:
             return dict(x=xn, u=un, J=J_new, error=False, delta_J=delta_J, succeeded=True, ls=ls, alpha=alpha,
                         ratio=ratio, dV1=dV1, trials=trials)
         if alpha > o["alpha_min_SQP_DDP"]:
@@ -262,37 +260,19 @@ def ilqr(model, cost, x, u, N, dt, options=None, soft=None, solve="canonical"):
         exit_code = 0
         while True:
             st = step(model, cost, x, u, N, dt, rho, J, o, soft, solve)
-            x, u, J, error, delta_J = st["x"], st["u"], st["J"], st["error"], st["delta_J"]
-            if st["succeeded"]:
-                drho = min(drho / o["rho_factor_SQP_DDP"], 1 / o["rho_factor_SQP_DDP"])
-                rho = max(rho * drho, o["rho_min_SQP_DDP"])
+            x, u, J = st["x"], st["u"], st["J"]
+            # (error == not succeeded: step() sets them together)
+            trace_rho, rho, drho, exit_code, it_next = state.step_outcome(o, st["error"], st["delta_J"], it, rho, drho)
             trace.append(dict(outer_iteration=outer, iteration=it, line_search_iteration=st["ls"],
-                              alpha=st["alpha"], rho=rho, J=J, dV1=st["dV1"], reduction_ratio=st["ratio"],
+                              alpha=st["alpha"], rho=trace_rho, J=J, dV1=st["dV1"], reduction_ratio=st["ratio"],
                               succeeded_line_search=st["succeeded"]))
-            exit_flag = False
-            if error:
-                drho = max(drho * o["rho_factor_SQP_DDP"], o["rho_factor_SQP_DDP"])
-                rho = max(rho * drho, o["rho_min_SQP_DDP"])
-                if rho > o["rho_max_SQP_DDP"]:
-                    exit_code, exit_flag = 2, True
-            elif delta_J < o["exit_tolerance_SQP_DDP"]:
-                exit_code, exit_flag = 1, True
-            if it == o["max_iter_SQP_DDP"] - 1:
-                exit_code, exit_flag = 3, True
-            else:
-                it += 1
-            if exit_flag:
+            it = it_next
+            if exit_code:
                 break
-        done = False
-        max_c = soft.max_value(x, u) if soft is not None else 0
-        if max_c < o["exit_tolerance_softConstraints"]:
-            exit_soft, done = 1, True
-        if outer == o["max_iter_softConstraints"] - 1:
-            exit_soft, done = 2, True
-        else:
-            outer += 1
-        if not done and soft.update(x, u):
-            exit_soft, done = 3, True
-        if done:
+        ex, outer = state.outer_exit(o, soft.max_value(x, u) if soft is not None else 0, outer)
+        if not ex and soft.update(x, u):
+            ex = 3
+        if ex:
+            exit_soft = ex
             break
     return dict(x=x, u=u, exit_code=exit_code, exit_soft=exit_soft, outer_iter=outer, iter=it, trace=trace)

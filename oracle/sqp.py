@@ -25,7 +25,7 @@ import copy
 
 import numpy as np
 
-from . import rbd
+from . import rbd, state
 
 
 class QuadCost:
@@ -290,15 +290,10 @@ def line_search(cost, model, x, u, xs, N, dt, dxul, J, merit, mu, o, soft=None, 
         if soft is not None:
             for j in soft.jacobians(x_new[:, N - 1], None, N - 1, N, nx):
                 D += float(j.dot(dxul[n * (N - 1):n * (N - 1) + nx, 0]))
-        merit_new = J_new + mu * c_new
-        delta_J = J - J_new
-        delta_merit = merit - merit_new
-        with np.errstate(divide="ignore", invalid="ignore"):
-            ratio = np.float64(delta_merit) / np.float64(alpha * (D - mu * c_new))
+        merit_new, ratio, accepted = state.sqp_trial(o, merit, J_new, c_new, D, alpha, mu)
         out = dict(alpha=alpha, ls=ls, x=x_new, u=u_new, J=J_new, c=c_new, merit=merit_new, D=D, ratio=ratio,
-                   delta_J=delta_J)
-        if (delta_merit >= 0 and ratio >= o["expected_reduction_min_SQP_DDP"]
-                and ratio <= o["expected_reduction_max_SQP_DDP"]):
+                   delta_J=J - J_new)
+        if accepted:
             out["succeeded_line_search"] = True
             return out
         elif alpha > o["alpha_min_SQP_DDP"]:
@@ -372,39 +367,20 @@ def sqp(model, cost, x, u, N, dt, method="PCG-SS", options=None, soft=None, warm
             error = not r["succeeded_line_search"]
             if not error:
                 x, u, J, c, merit = r["x"], r["u"], r["J"], r["c"], r["merit"]
-                drho = min(drho / o["rho_factor_SQP_DDP"], 1 / o["rho_factor_SQP_DDP"])
-                rho = max(rho * drho, o["rho_min_SQP_DDP"])
-            delta_J = r["delta_J"]
+            # reduce_regularization / check_for_exit_or_error (:457-481); the trace row records the rho between them
+            trace_rho, rho, drho, exit_sqp, it_next = state.step_outcome(o, error, r["delta_J"], it, rho, drho)
             trace.append(dict(outer_iteration=outer, iteration=it, line_search_iteration=r["ls"], alpha=r["alpha"],
-                              rho=rho, J=J, c=c, merit=merit, D=r["D"], reduction_ratio=r["ratio"],
+                              rho=trace_rho, J=J, c=c, merit=merit, D=r["D"], reduction_ratio=r["ratio"],
                               succeeded_line_search=not error))
-            # check_for_exit_or_error (:463-481)
-            exit_flag = False
-            if error:
-                drho = max(drho * o["rho_factor_SQP_DDP"], o["rho_factor_SQP_DDP"])
-                rho = max(rho * drho, o["rho_min_SQP_DDP"])
-                if rho > o["rho_max_SQP_DDP"]:
-                    exit_sqp, exit_flag = 2, True
-            elif delta_J < o["exit_tolerance_SQP_DDP"]:
-                exit_sqp, exit_flag = 1, True
-            if it == o["max_iter_SQP_DDP"] - 1:
-                exit_sqp, exit_flag = 3, True
-            else:
-                it += 1
-            if exit_flag:
+            it = it_next
+            if exit_sqp:
                 break
         # check_and_update_soft_constraints (:483-508); without soft limits the max value is 0 < tol
-        done = False
-        max_c = soft.max_value(x, u) if soft is not None else 0
-        if max_c < o["exit_tolerance_softConstraints"]:
-            exit_soft, done = 1, True
-        if outer == o["max_iter_softConstraints"] - 1:
-            exit_soft, done = 2, True
-        else:
-            outer += 1
-        if not done and soft.update(x, u):
-            exit_soft, done = 3, True
-        if done:
+        ex, outer = state.outer_exit(o, soft.max_value(x, u) if soft is not None else 0, outer)
+        if not ex and soft.update(x, u):
+            ex = 3
+        if ex:
+            exit_soft = ex
             break
     return dict(x=x, u=u, exit_sqp=exit_sqp, exit_soft=exit_soft, outer_iter=outer, sqp_iter=it, trace=trace,
                 pcg_iters=pcg_iters, dxul=dxuls, active_rows=active_rows, active_sets=active_sets,

@@ -13,12 +13,11 @@
 //                    rollout u^ = u + alpha d + K (x^ - x), x^+ = f(x^, u^) with
 //                    the articulated-body dynamics in registers, and the trial
 //                    cost; all trials alpha = 1, f, f^2, ... speculatively;
-//   k_ilqr_decide    per problem: the acceptance test in the reference's alpha
-//                    order, the rho schedule / exit codes of the SQP
-//                    (:457-481), the trace row and the copy of the accepted
-//                    trajectory.
+//   k_ilqr_decide    (tmpc_state.hip) per problem: the acceptance test in the
+//                    reference's alpha order, the rho schedule / exit codes of
+//                    the SQP (:457-481), the trace row and the copy of the
+//                    accepted trajectory.
 #include "tmpc_internal.h"
-#include "tmpc_copy.h"
 
 namespace tmpc {
 
@@ -1034,134 +1033,6 @@ __global__ void __launch_bounds__(256) k_ilqr_soft_jac(const ConstrDev* __restri
   for (int m = 0; m < 3 * NJ; ++m) jout[(size_t)gid * 3 * NJ + m] = jac[m];
 }
 
-// ======================================================================= decision + state machine
-// One 64-lane workgroup per problem.  Acceptance ratio (J - J^) / (-alpha (dV1 + alpha dV2)) in
-// [exp_red_min, exp_red_max] in the reference's alpha order (oracle/ilqr.py), rho schedule and exit
-// codes of reduce_regularization / check_for_exit_or_error (:457-481), trace row, trajectory copy.
-#ifndef TMPC_TRK_PART   // (not a template: in the fixed-goal translation unit only)
-__global__ void __launch_bounds__(64) k_ilqr_decide(PList P, int B, int N, int NX, int NU, int T, int init,
-                                                    const double* __restrict__ alphas, SolverOpts o,
-                                                    const double* __restrict__ Jt, const double* __restrict__ dV,
-                                                    const int* __restrict__ okb, const double* __restrict__ xt,
-                                                    const double* __restrict__ ut, double* __restrict__ x,
-                                                    double* __restrict__ u, ProbState st, TraceDev tr,
-                                                    int* __restrict__ active_count,
-                                                    unsigned long long* __restrict__ counters,
-                                                    int* __restrict__ activate) {
-  if (!P.has(blockIdx.x, B)) return;
-  const int b = P.at(blockIdx.x);
-  if (!st.active[b]) return;
-  __shared__ int s_choice;
-  __shared__ double s_al[64], s_J[64];
-  const int t = threadIdx.x;
-  const int W = o.max_iter_sqp + 1;
-  const int K = N - 1;
-  if (t < T) {   // the trials' alphas and costs loaded by their lanes at once (lane 0 walks them below)
-    s_al[t] = alphas[t];
-    s_J[t] = Jt[(size_t)b * T + t];
-  }
-  __syncthreads();
-  if (t == 0) {
-    if (init) {
-      const double J = s_J[0];
-      st.J[b] = J;
-      st.c[b] = 0.0;
-      st.merit[b] = J;
-      const size_t e = (size_t)b * W;
-      tr.iteration[e] = 0; tr.ls_iter[e] = 0; tr.alpha[e] = 1.0; tr.rho[e] = st.rho[b];
-      tr.J[e] = J; tr.c[e] = 0.0; tr.merit[e] = J; tr.D[e] = __builtin_nan(""); tr.ratio[e] = __builtin_nan("");
-      tr.accepted[e] = 0; tr.pcg_iters[e] = 0;
-      *active_count = 1;   // the host only tests for zero
-      if (activate) {      // a restarted pass / a stream's new problem enters its inner loop (st.active: act_init)
-        st.active[b] = 0;
-        activate[b] = 1;
-      }
-      s_choice = -1;
-    } else {
-      const double J = st.J[b];
-      double rho = st.rho[b], drho = st.drho[b];
-      const bool bok = okb[b] != 0;
-      const double dV1 = dV[2 * b], dV2 = dV[2 * b + 1];
-      int choice = -1, ls = 0;
-      double al = 0.0, ratio = __builtin_nan(""), Jn = J, deltaJ = 0.0;
-      if (bok) {
-        for (int tt = 0; tt < T; ++tt) {
-          al = s_al[tt];
-          ls = tt;
-          Jn = s_J[tt];
-          deltaJ = J - Jn;
-          ratio = deltaJ / (-al * (dV1 + al * dV2));
-          if (ratio >= o.exp_red_min && ratio <= o.exp_red_max) {
-            choice = tt;
-            break;
-          }
-        }
-      }
-      const bool error = choice < 0;
-      const int it = st.iter[b];
-      const size_t e = (size_t)b * W + it + 1;
-      if (counters) {
-        // per-problem tallies [B][3], summed once per solve (k_sum_counters): [0] problem-iterations,
-        // [2] iterations with a fresh dynamics gradient (same-address atomics serialised the launch)
-        unsigned long long* pc = counters + (size_t)b * 3;
-        pc[0] += 1ull;
-        pc[2] += (unsigned long long)st.need_grad[b];
-      }
-      if (!error) {
-        st.J[b] = Jn;
-        st.merit[b] = Jn;
-        drho = fmin(drho / o.rho_factor, 1.0 / o.rho_factor);
-        rho = fmax(rho * drho, o.rho_min);
-      }
-      tr.iteration[e] = it; tr.ls_iter[e] = bok ? ls : 0; tr.alpha[e] = bok ? al : 0.0; tr.rho[e] = rho;
-      tr.J[e] = error ? J : Jn; tr.c[e] = 0.0; tr.merit[e] = error ? J : Jn;
-      tr.D[e] = bok ? dV1 : __builtin_nan(""); tr.ratio[e] = bok ? ratio : __builtin_nan("");
-      tr.accepted[e] = error ? 0 : 1; tr.pcg_iters[e] = 0;
-      bool done = false;
-      if (error) {
-        drho = fmax(drho * o.rho_factor, o.rho_factor);
-        rho = fmax(rho * drho, o.rho_min);
-        if (rho > o.rho_max) { st.exit_sqp[b] = 2; done = true; }
-      } else if (deltaJ < o.exit_tol_sqp) {
-        st.exit_sqp[b] = 1;
-        done = true;
-      }
-      if (it == o.max_iter_sqp - 1) {
-        st.exit_sqp[b] = 3;
-        done = true;
-      } else {
-        st.iter[b] = it + 1;
-      }
-      st.rho[b] = rho;
-      st.drho[b] = drho;
-      st.need_grad[b] = (error || done) ? 0 : 1;
-      if (done) st.active[b] = 0;
-      else *active_count = 1;
-      s_choice = choice;
-    }
-  }
-  __syncthreads();
-  const int choice = s_choice;
-  if (choice >= 0) {
-    const double* xs_ = xt + ((size_t)b * T + choice) * NX * N;
-    const double* us_ = ut + ((size_t)b * T + choice) * NU * K;
-    // trial trajectories are knot-major ([k][m], see k_ilqr_forward); x / u the reference's [m][k]; the
-    // loads of U passes ahead of their stores (tmpc_copy.h)
-    double* xb = x + (size_t)b * NX * N;
-    double* ub = u + (size_t)b * NU * K;
-    wg_batched<12, double>(NX * N, t, 64, [&](int e) {
-      const int m = e / N, k = e - m * N;
-      return xs_[k * NX + m];
-    }, [&](int e, double v) { xb[e] = v; });
-    wg_batched<8, double>(NU * K, t, 64, [&](int e) {
-      const int m = e / K, k = e - m * K;
-      return us_[k * NU + m];
-    }, [&](int e, double v) { ub[e] = v; });
-  }
-}
-
-#endif   // TMPC_TRK_PART
-
 // ======================================================================= launchers
 
 // the backward sweep and the initial cost depend on the joint count only
@@ -1285,13 +1156,5 @@ int TMPC_TRK_FN(launch_ilqr_init_cost)(hipStream_t s, int nj, const IlqrArgs& a)
   return for_nj<1, NJMAX>(nj, [&](auto n) { LaunchIlqrNJ<decltype(n)::value>::template init_cost<kTrkPart>(s, a); });
 }
 #undef TMPC_TRK_FN
-
-#ifndef TMPC_TRK_PART
-void launch_ilqr_decide(hipStream_t s, const DecideArgs& a) {
-  hipLaunchKernelGGL(k_ilqr_decide, dim3(a.B), dim3(64), 0, s, a.P, a.B, a.N, a.NX, a.NU, a.T, a.init, a.alphas, a.o, a.Jt,
-                     a.dV, a.ok, a.xt, a.ut, a.x, a.u, a.st, a.tr, a.active_count, a.counters, a.activate);
-}
-
-#endif   // TMPC_TRK_PART
 
 }  // namespace tmpc

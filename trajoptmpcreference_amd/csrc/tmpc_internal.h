@@ -1,5 +1,5 @@
-// Internal declarations shared by the kernels (tmpc_kernels.hip) and the
-// C-ABI / solver driver (tmpc_api.cpp).
+// Internal declarations shared by the kernels (the QP side in tmpc_kernels.hip, the solve loops' state
+// machine in tmpc_state.hip, ...) and the C-ABI / solver driver (tmpc_api.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -7,6 +7,7 @@
 
 #include "tmpc_device.h"
 #include "tmpc_models.h"
+#include "tmpc_state.h"   // SolverOpts and the state machine's scalar rules
 
 struct tmpc_ctx;
 
@@ -36,23 +37,6 @@ void launch_alive_list(hipStream_t s, int B, const int* alive, int* idx, int* cn
 enum { PRECOND_J = 1, PRECOND_BJ = 2, PRECOND_SS = 3, PRECOND_NONE = 4 };
 enum { LS_MODE_INIT = 0, LS_MODE_STEP = 1 };
 enum { QP_MODE_PCG = 0, QP_MODE_SCHUR = 1, QP_MODE_DXU = 2 };
-
-// set_default_options (TrajoptMPCReference.py:91-115) + the fixed merit
-// weight mu = 10 (:545-546)
-struct SolverOpts {
-  double exit_tol_sqp;
-  double alpha_factor;
-  double alpha_min;
-  double rho_factor;
-  double rho_min;
-  double rho_max;
-  double rho_init;
-  double exp_red_min;
-  double exp_red_max;
-  double mu;
-  int max_iter_sqp;
-  int pad;
-};
 
 // per-problem solver state (device arrays, SoA)
 struct ProbState {
@@ -267,7 +251,7 @@ struct SoftOuterArgs : Batch {
   int max_iter;
   double *x, *u, *mu, *lam, *phi;
   int *outer_active, *outer_iter, *exit_soft, *outer_count;
-  // the per-problem outer loop (null act_init: lock-step, tmpc_kernels.hip)
+  // the per-problem outer loop (null act_init: lock-step, tmpc_state.hip)
   ProbState st;
   int* act_init;
   double rho_init;
