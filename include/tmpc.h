@@ -38,7 +38,8 @@ extern "C" {
 #endif
 
 #define TMPC_ABI_VERSION 12  /* 12: tmpc_qp_last_inputs; 11: tmpc_ilqr_step_batch (later added, same version:
-                                tmpc_set_reference, tmpc_set_reference_device); 10: tmpc_*_solve_stream_device;
+                                tmpc_set_reference, tmpc_set_reference_device, tmpc_mpc_step,
+                                tmpc_mpc_step_device); 10: tmpc_*_solve_stream_device;
                                 9: tmpc_pcg_dense_batch; 8: tmpc_qp_blocks_batch */
 
 /* SQPSolverMethods (TrajoptMPCReference.py:13-18). */
@@ -304,6 +305,32 @@ int tmpc_mpc_batch(tmpc_ctx* ctx, int B, int N, double dt, int solver, int steps
                    double* x_exec, double* u_exec, int32_t* exit_codes, int32_t* iters);
 int tmpc_mpc_batch_device(tmpc_ctx* ctx, int B, int N, double dt, int solver, int steps, double* d_x, double* d_u,
                           double* d_x_exec, double* d_u_exec, int32_t* d_exit_codes, int32_t* d_iters);
+
+/* One step of that loop against a plant the caller measures (closed-loop MPC): the call returns after one
+ * horizon solve with the control to apply, and the next call restarts the horizon from the measured state.
+ * Per call: x[:, 0] <- x_meas when given (the rest of the warm start stays); the horizon solve with the
+ * reference window at column `step`; then what tmpc_mpc_batch does between two solves, in one launch -- u0,
+ * x_pred = integrator(x[:, 0], u[:, 0]) and status out, x and u shifted by one knot (last kept) with
+ * x[:, 0] = x_pred, the PCG warm start (pcg_warm_start) and the soft-limit constants shifted -- and
+ * QF_start -= 1 (floor 0) when set.  `steps` calls with x_meas NULL, or with x_meas the previous call's x_pred,
+ * are tmpc_mpc_batch(steps) bit for bit.
+ * step: the index since the loop began.  0 starts a loop as tmpc_mpc_batch's first step does (warm lambda
+ * zeroed, the soft state as the context holds it for this B, N).  s > 0 is accepted only when the context's
+ * previous solve was step s - 1 of the same (B, N, dt, solver): any other solve, stream or change of the
+ * context's configuration in between fails the call with what it expected (the warm lambda and soft constants
+ * on the device would be another solve's).  Refusals otherwise: tmpc_mpc_batch's.
+ * The io arrays (each nullable) are device pointers for tmpc_mpc_step_device and host pointers for
+ * tmpc_mpc_step, which also takes x [B][nx][N], u [B][nu][N-1] on the host (in: the horizon, out: shifted). */
+typedef struct tmpc_mpc_io {
+  const double* x_meas; /* [B][nx] measured state for this step; NULL: keep x[:, 0] (the model's own prediction) */
+  double* u0;           /* [B][nu] out: the control to apply, u[:, 0] of this step's solve */
+  double* x_pred;       /* [B][nx] out: integrator(x0, u0), the nominal next state (fp64 in every precision mode) */
+  int32_t* status;      /* [B][2] out: exit code, iterations of this step's solve */
+} tmpc_mpc_io;
+int tmpc_mpc_step_device(tmpc_ctx* ctx, int B, int N, double dt, int solver, int step, double* d_x, double* d_u,
+                         const tmpc_mpc_io* io);
+int tmpc_mpc_step(tmpc_ctx* ctx, int B, int N, double dt, int solver, int step, double* x, double* u,
+                  const tmpc_mpc_io* io);
 
 /* Euler rollout x_{k+1} = f(x_k, u_k) from x[:, 0] (device pointers), the §8d initial trajectory. */
 int tmpc_rollout_batch_device(tmpc_ctx* ctx, int B, int N, double dt, double* d_x, const double* d_u);

@@ -10,11 +10,11 @@ from .constraint import BoxConstraint, TrajoptConstraint
 from .cost import QuadraticCost, TrackingCost, TrajoptCost, UrdfCost
 from .pcg import PCG
 from .plant import PendulumPlant, TrajoptPlant, URDFPlant
-from .solver import MPCSolverMethods, SQPSolverMethods, TrajoptMPCReference
+from .solver import MPCSession, MPCSolverMethods, SQPSolverMethods, TrajoptMPCReference
 from .urdf import RobotModel, parse_urdf, pendulum_urdf, planar_arm_urdf
 
 __all__ = [
     "BoxConstraint", "TrajoptConstraint", "QuadraticCost", "TrackingCost", "TrajoptCost", "UrdfCost", "PCG", "TrajoptPlant", "URDFPlant",
-    "PendulumPlant", "MPCSolverMethods", "SQPSolverMethods", "TrajoptMPCReference", "RobotModel", "parse_urdf",
+    "PendulumPlant", "MPCSession", "MPCSolverMethods", "SQPSolverMethods", "TrajoptMPCReference", "RobotModel", "parse_urdf",
     "pendulum_urdf", "planar_arm_urdf",
 ]

@@ -72,6 +72,12 @@ class tmpc_stream(C.Structure):
                 ("status", C.c_void_p), ("trace", tmpc_trace)]
 
 
+class tmpc_mpc_io(C.Structure):
+    """one MPC step's measurement and outputs (tmpc_mpc_step: host arrays, tmpc_mpc_step_device: device
+    arrays), each nullable; include/tmpc.h"""
+    _fields_ = [("x_meas", C.c_void_p), ("u0", C.c_void_p), ("x_pred", C.c_void_p), ("status", C.c_void_p)]
+
+
 TRACE_FIELDS = [("iteration", np.int32), ("line_search_iteration", np.int32), ("alpha", np.float64),
                 ("rho", np.float64), ("J", np.float64), ("c", np.float64), ("merit", np.float64),
                 ("D", np.float64), ("reduction_ratio", np.float64), ("succeeded_line_search", np.int32),
@@ -109,6 +115,10 @@ SIGNATURES = {
                                  _ip, _ip]),
     "tmpc_mpc_batch_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tmpc_mpc_step": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp,
+                                C.POINTER(tmpc_mpc_io)]),
+    "tmpc_mpc_step_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.POINTER(tmpc_mpc_io)]),
     "tmpc_rollout_batch_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "tmpc_fd_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     "tmpc_fd_grad_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp]),
@@ -416,6 +426,38 @@ class Context:
         sid = SOLVER_ILQR if solver == "iLQR" else LINSYS[solver]
         self._check(self.lib.tmpc_mpc_batch_device(self.h, B, int(N), float(dt), sid, int(steps), d_x, d_u, d_xe, d_ue,
                                                    d_codes, d_iters), "tmpc_mpc_batch_device")
+
+    def mpc_step_device(self, B, N, dt, solver, step, d_x, d_u, d_x_meas=None, d_u0=None, d_x_pred=None,
+                        d_status=None):
+        """One step of the receding-horizon loop from a measured state (tmpc_mpc_step_device): device
+        pointers d_x [B][nx][N], d_u [B][nu][N-1] (the horizon, shifted on return), d_x_meas [B][nx] (None: the
+        model's own prediction), and the outputs d_u0 [B][nu], d_x_pred [B][nx], d_status [B][2] int32 (each
+        nullable).  step = 0 starts a loop; step s > 0 must follow step s - 1 of the same loop on this
+        context with no other solve in between."""
+        sid = SOLVER_ILQR if solver == "iLQR" else LINSYS[solver]
+        io = tmpc_mpc_io(x_meas=d_x_meas, u0=d_u0, x_pred=d_x_pred, status=d_status)
+        self._check(self.lib.tmpc_mpc_step_device(self.h, int(B), int(N), float(dt), sid, int(step), d_x, d_u,
+                                                  C.byref(io)), "tmpc_mpc_step_device")
+
+    def mpc_step(self, x, u, N, dt, solver, step, x_meas=None):
+        """mpc_step_device on host arrays (tmpc_mpc_step): x [B][nx][N], u [B][nu][N-1] in, the shifted horizon
+        out with u0 [B][nu], x_pred [B][nx] and the solve's exit codes / iterations [B]."""
+        x = _c64(x).copy()
+        u = _c64(u).copy()
+        self._check_traj(x, u, N)
+        B, nx, _ = x.shape
+        nu = u.shape[1]
+        if x_meas is not None:
+            x_meas = _c64(x_meas)
+            if x_meas.shape != (B, nx):
+                raise ValueError(f"x_meas must be [B][nx] = {(B, nx)}, got {x_meas.shape}")
+        u0, xp, status = np.zeros((B, nu)), np.zeros((B, nx)), np.zeros((B, 2), dtype=np.int32)
+        sid = SOLVER_ILQR if solver == "iLQR" else LINSYS[solver]
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        io = tmpc_mpc_io(x_meas=vp(x_meas), u0=vp(u0), x_pred=vp(xp), status=vp(status))
+        self._check(self.lib.tmpc_mpc_step(self.h, B, int(N), float(dt), sid, int(step), _ptr(x), _ptr(u),
+                                           C.byref(io)), "tmpc_mpc_step")
+        return dict(x=x, u=u, u0=u0, x_pred=xp, exit_code=status[:, 0].copy(), iters=status[:, 1].copy())
 
     def ilqr_solve_batch_device(self, B, N, dt, d_x, d_u, want_status=False):
         ex = np.zeros(B, dtype=np.int32) if want_status else None

@@ -93,6 +93,7 @@ int set_cost(tmpc_ctx* ctx, const CostDev& c) {
   HIP_OK(hipStreamSynchronize(ctx->stream));
   ctx->hcost = c;
   ctx->has_cost = true;
+  ctx->mpc_last.B = 0;   // (QF_start counts down along an MPC step loop)
   return 0;
 }
 
@@ -200,6 +201,7 @@ int tmpc_set_model(tmpc_ctx* ctx, int n, const int32_t* parent, const int32_t* j
   const char* gen = getenv("TMPC_GENERIC_MODEL");
   ctx->model_id = (gen && gen[0] == '1') ? 0 : match_static_model(m);
   ctx->soft_B = ctx->soft_N = -1;   // the soft-constraint state is sized per model (6 n slots per knot)
+  ctx->mpc_last.B = 0;
   ctx->ref_dev = nullptr;           // and so is a state reference (nx rows)
   ctx->ref_R = ctx->ref_M = 0;
   hipSetDevice(ctx->device);
@@ -327,6 +329,7 @@ int tmpc_set_box_limits(tmpc_ctx* ctx, const tmpc_box_limits* L) {
   HIP_OK(hipStreamSynchronize(ctx->stream));
   ctx->hlim = c;
   ctx->soft_B = ctx->soft_N = -1;
+  ctx->mpc_last.B = 0;
   return 0;
 }
 
@@ -347,6 +350,7 @@ int tmpc_set_soft_state(tmpc_ctx* ctx, int B, int N, const double* mu, const dou
   HIP_OK(hipStreamSynchronize(ctx->stream));
   ctx->soft_B = B;
   ctx->soft_N = N;
+  ctx->mpc_last.B = 0;
   return 0;
 }
 
@@ -371,6 +375,7 @@ int tmpc_set_options(tmpc_ctx* ctx, const tmpc_options* o) {
   if (o->precision < TMPC_PRECISION_F64 || o->precision > TMPC_PRECISION_MIXED)
     return fail(ctx, "precision %d (valid: 0 F64, 1 F32, 2 MIXED)", o->precision);
   ctx->opts = *o;
+  ctx->mpc_last.B = 0;   // (pcg_warm_start, the precision: an MPC step loop keeps its options)
   return 0;
 }
 
@@ -454,6 +459,45 @@ int tmpc_mpc_batch(tmpc_ctx* ctx, int B, int N, double dt, int solver, int steps
   if (u_exec) HIP_OK(hipMemcpy(u_exec, mpc_ue, sizeof(double) * B * nu * steps, hipMemcpyDeviceToHost));
   if (exit_codes) HIP_OK(hipMemcpy(exit_codes, mpc_codes, sizeof(int) * B * steps, hipMemcpyDeviceToHost));
   if (iters) HIP_OK(hipMemcpy(iters, mpc_iters, sizeof(int) * B * steps, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int tmpc_mpc_step_device(tmpc_ctx* ctx, int B, int N, double dt, int solver, int step, double* d_x, double* d_u,
+                         const tmpc_mpc_io* io) {
+  if (!ctx) return -1;
+  hipSetDevice(ctx->device);
+  return mpc_step_device(ctx, B, N, dt, solver, step, d_x, d_u, io ? *io : tmpc_mpc_io{});
+}
+
+int tmpc_mpc_step(tmpc_ctx* ctx, int B, int N, double dt, int solver, int step, double* x, double* u,
+                  const tmpc_mpc_io* io) {
+  if (!ctx) return -1;
+  int rc = check_ready(ctx, B, N, solver != TMPC_SOLVER_ILQR);
+  if (rc) return rc;
+  if (!x || !u) return fail(ctx, "null x/u");
+  hipSetDevice(ctx->device);
+  const tmpc_mpc_io h = io ? *io : tmpc_mpc_io{};
+  const int nx = ctx->hcost.nx, nu = ctx->hcost.nu;
+  const size_t xn = (size_t)B * nx * N, un = (size_t)B * nu * (N - 1);
+  BUF(double, step_x, xn);
+  BUF(double, step_u, un);
+  BUF(double, step_xm, (size_t)B * nx);
+  BUF(double, step_u0, (size_t)B * nu);
+  BUF(double, step_xp, (size_t)B * nx);
+  BUF(int, step_status, (size_t)B * 2);
+  HIP_OK(hipMemcpyAsync(step_x, x, xn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIP_OK(hipMemcpyAsync(step_u, u, un * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if (h.x_meas)
+    HIP_OK(hipMemcpyAsync(step_xm, h.x_meas, sizeof(double) * B * nx, hipMemcpyHostToDevice, ctx->stream));
+  tmpc_mpc_io d{};
+  d.x_meas = h.x_meas ? step_xm : nullptr;
+  d.u0 = step_u0; d.x_pred = step_xp; d.status = step_status;
+  if ((rc = mpc_step_device(ctx, B, N, dt, solver, step, step_x, step_u, d))) return rc;
+  HIP_OK(hipMemcpy(x, step_x, xn * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(u, step_u, un * sizeof(double), hipMemcpyDeviceToHost));
+  if (h.u0) HIP_OK(hipMemcpy(h.u0, step_u0, sizeof(double) * B * nu, hipMemcpyDeviceToHost));
+  if (h.x_pred) HIP_OK(hipMemcpy(h.x_pred, step_xp, sizeof(double) * B * nx, hipMemcpyDeviceToHost));
+  if (h.status) HIP_OK(hipMemcpy(h.status, step_status, sizeof(int) * B * 2, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -68,6 +68,10 @@ struct tmpc_ctx {
   // soft_Gk); cleared by every other user of those buffers (alloc_work), so stale data is refused.  nj, QF_start:
   // the model and cost of that call, which lay the Ghat blocks out
   struct { int B, N, nj, QF_start; bool soft, banded; } qp_last{0, 0, 0, -1, false, false};   // B = 0: none
+  // the last tmpc_mpc_step[_device]: what the warm lambda, the soft constants and QF_start on the device continue
+  // (step + 1 of the same loop is the only step accepted next); cleared by every other solve (alloc_state) and
+  // by every change of the configuration, so another solve's state is refused
+  struct { int B, N, solver, step; double dt; } mpc_last{0, 0, 0, 0, 0.0};   // B = 0: none
   std::map<std::string, double> kbytes;   // bytes beyond registers / LDS of counting kernels since tmpc_reset_stats
   std::vector<tmpc_ctx*> subs;            // a stream's concurrent sub-streams (tmpc_stream.substreams): own HIP
                                           // stream and buffers each, the configuration copied from this context
@@ -321,6 +325,9 @@ int ilqr_device(tmpc_ctx* ctx, int B, int N, double dt, double* d_x, double* d_u
 int stream_solve(tmpc_ctx* ctx, int N, double dt, int linsys, const tmpc_stream* s);
 int mpc_device(tmpc_ctx* ctx, int B, int N, double dt, int solver, int steps, double* d_x, double* d_u,
                double* d_xe, double* d_ue, int* d_codes, int* d_iters);
+// one step of that loop from a measured state (include/tmpc.h tmpc_mpc_io: device pointers)
+int mpc_step_device(tmpc_ctx* ctx, int B, int N, double dt, int solver, int step, double* d_x, double* d_u,
+                    const tmpc_mpc_io& io);
 // The goal window of a horizon solve (tmpc_internal.h launch_goal_window): null without a reference.  What a
 // reference cannot be combined with (UrdfCost; R not 1 or `rows`, the batch size or the stream's period) is
 // refused here.  pid / pbase / mask: a stream's slots (null / 0 / null: problem b, every problem).

@@ -352,6 +352,115 @@ __global__ void __launch_bounds__(64) k_mpc_shift(MT M, int B, int N, double dt,
   }
 }
 
+// ======================================================================= MPC step, handed back (tmpc_mpc_step_device)
+// Everything the loop does between two horizon solves, for a caller that closes the loop itself: one 64-lane
+// workgroup per problem.  Lane 0 takes the Euler step with k_mpc_shift's operation sequence (the bits of x_pred are
+// the loop's x_exec) while lane 1 copies the solve's status; then the lanes spread along the knots, 64 per chunk.
+// A row shifts in place, so a chunk's last lane reads the element the next chunk's first lane writes (64 c + 64):
+// every lane loads its knot k + 1 of all rows -- x, u and the warm lambda's block, which shifts by the same
+// rule -- into registers, the workgroup meets at a barrier, then every lane stores to knot k.  Chunks ascend, so
+// a chunk's stores (knots < 64 c + 64) never reach what a later chunk still has to load (knots > 64 c + 64).
+// The soft constants follow k_soft_shift's rule: knot 0 takes knot 1's value and every later knot of the slot's
+// span (torque limits: N - 1 knots) returns to soft_initial; lane sl < 6 NJ holds slot sl's knot-1 values over
+// the barrier while all lanes write the constants, 64 consecutive elements per pass.
+template <int NJ, bool CHAIN, class MT>
+__global__ void __launch_bounds__(64) k_mpc_advance(MT M, AdvanceArgs a) {
+  constexpr int NX = 2 * NJ, NU = NJ, MC = 6 * NJ;
+  static_assert(MC <= 64, "one lane per soft slot");
+  const int b = blockIdx.x, t = threadIdx.x;
+  const int N = a.N, K = N - 1;
+  double* xb = a.x + (size_t)b * NX * N;
+  double* ub = a.u + (size_t)b * NU * K;
+  __shared__ double xn[NX];
+  if (t == 0) {
+    // the simulated plant is fp64 in every precision mode
+    double q[NJ], qd[NJ], uu[NJ], qdd[NJ], cq[NJ], sq[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      q[j] = xb[j * N];
+      qd[j] = xb[(NJ + j) * N];
+      uu[j] = ub[j * K];
+      joint_cs(M, j, q[j], cq[j], sq[j]);
+    }
+    fd_aba<NJ, CHAIN>(M, cq, sq, qd, uu, qdd);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      xn[j] = __dadd_rn(q[j], __dmul_rn(a.dt, qd[j]));
+      xn[NJ + j] = __dadd_rn(qd[j], __dmul_rn(a.dt, qdd[j]));
+    }
+    if (a.x_pred) {
+#pragma unroll
+      for (int m = 0; m < NX; ++m) a.x_pred[(size_t)b * NX + m] = xn[m];
+    }
+    if (a.u0) {
+#pragma unroll
+      for (int m = 0; m < NU; ++m) a.u0[(size_t)b * NU + m] = uu[m];
+    }
+  }
+  if (t == 1 && a.status) {
+    a.status[2 * b] = a.exit_code[b];
+    a.status[2 * b + 1] = a.iter[b];
+  }
+  __syncthreads();
+  double* lw = a.lam_warm ? a.lam_warm + (size_t)b * N * NX : nullptr;
+  for (int c0 = 0; c0 < K; c0 += 64) {   // (uniform bounds: every lane meets every barrier)
+    const int k = c0 + t;
+    const bool on = k < K, on_u = k + 1 < K;
+    double xv[NX], uv[NU], lv[NX];
+    if (on) {
+#pragma unroll
+      for (int m = 0; m < NX; ++m) xv[m] = xb[m * N + k + 1];
+      if (on_u) {
+#pragma unroll
+        for (int m = 0; m < NU; ++m) uv[m] = ub[m * K + k + 1];
+      }
+      if (lw) {
+#pragma unroll
+        for (int m = 0; m < NX; ++m) lv[m] = lw[(size_t)(k + 1) * NX + m];
+      }
+    }
+    __syncthreads();
+    if (on) {
+#pragma unroll
+      for (int m = 0; m < NX; ++m) xb[m * N + k] = k == 0 ? xn[m] : xv[m];
+      if (on_u) {
+#pragma unroll
+        for (int m = 0; m < NU; ++m) ub[m * K + k] = uv[m];
+      }
+      if (lw) {
+#pragma unroll
+        for (int m = 0; m < NX; ++m) lw[(size_t)k * NX + m] = lv[m];
+      }
+    }
+  }
+  if (a.mu) {
+    const size_t off = (size_t)b * N * MC;
+    double* arrs[3] = {a.mu + off, a.lam + off, a.phi + off};
+    SoftInit si[3];
+#pragma unroll
+    for (int ty = 0; ty < 3; ++ty) si[ty] = soft_initial(a.Cs, ty);
+    double first[3] = {0.0, 0.0, 0.0};
+    if (t < MC) {
+#pragma unroll
+      for (int r = 0; r < 3; ++r) first[r] = arrs[r][MC + t];
+    }
+    __syncthreads();
+    for (int i = MC + t; i < N * MC; i += 64) {
+      const int k = i / MC, ty = (i - k * MC) / (2 * NJ);
+      if (k < (ty == 2 ? N - 1 : N)) {
+        const SoftInit s = ty == 0 ? si[0] : ty == 1 ? si[1] : si[2];
+        arrs[0][i] = s.mu;
+        arrs[1][i] = s.lam;
+        arrs[2][i] = s.phi;
+      }
+    }
+    if (t < MC && (t / (2 * NJ) == 2 ? N - 1 : N) > 1) {
+#pragma unroll
+      for (int r = 0; r < 3; ++r) arrs[r][t] = first[r];
+    }
+  }
+}
+
 template <int NJ, bool CHAIN, class MT>
 struct LaunchFD {
   static void qp_fd(bool f32, hipStream_t s, const ModelDev* M, const DynArgs& a) {
@@ -389,6 +498,11 @@ struct LaunchFD {
   static void mpc_shift(hipStream_t s, const ModelDev* M, const ShiftArgs& a) {
     hipLaunchKernelGGL((k_mpc_shift<NJ, CHAIN, MT>), dim3(a.B), dim3(64), 0, s, MT::make(M), a.B, a.N, a.dt, a.step,
                        a.steps, a.x, a.u, a.xe, a.ue);
+  }
+  // (the MPC entry points refuse a wide model: no instance)
+  static void mpc_advance(hipStream_t s, const ModelDev* M, const AdvanceArgs& a) {
+    if constexpr (!kWide<NJ>)
+      hipLaunchKernelGGL((k_mpc_advance<NJ, CHAIN, MT>), dim3(a.B), dim3(64), 0, s, MT::make(M), a);
   }
   static void rollout(bool f32, hipStream_t s, const ModelDev* M, const Batch& b, double dt, double* x, const double* u,
                       const int* mask) {
@@ -438,6 +552,14 @@ int launch_mpc_shift(hipStream_t s, const ModelSel& m, const ShiftArgs& a) {
   return dispatch_model(m.mid, m.nj, m.chain, [&](auto t) {
     using T = decltype(t);
     LaunchFD<T::nj, T::chain, typename T::model>::mpc_shift(s, m.M, a);
+  });
+}
+
+int launch_mpc_advance(hipStream_t s, const ModelSel& m, const AdvanceArgs& a) {
+  if (m.nj > NJ_FULL) return -2;
+  return dispatch_model(m.mid, m.nj, m.chain, [&](auto t) {
+    using T = decltype(t);
+    LaunchFD<T::nj, T::chain, typename T::model>::mpc_advance(s, m.M, a);
   });
 }
 

@@ -299,6 +299,29 @@ struct ShiftArgs {
 };
 int launch_mpc_shift(hipStream_t s, const ModelSel& m, const ShiftArgs& a);
 
+// BoxConstraint.__init__ (:21-24) for a slot of soft type t: mu = mu_init, lambda = 0, phi = phi_init
+struct SoftInit { double mu, lam, phi; };
+__device__ __forceinline__ SoftInit soft_initial(const ConstrDev* __restrict__ Cs, int t) {
+  return {Cs->mu_init[t], 0.0, Cs->phi_init[t]};
+}
+
+// One step of the MPC loop handed back to the caller (tmpc_mpc_step_device), everything between two horizon solves
+// in one launch: x_0, u_0 through the plant into x_pred / u0 [B][nx] / [B][nu] (launch_mpc_shift's operations), the
+// solve's exit code and iterations into status [B][2], the trajectory shifted by one knot with x_0 = x_pred, the PCG
+// warm start lam_warm [B][N][nx] shifted by one block (last kept), the soft constants mu / lam / phi [B][N][6 nj]
+// shifted by launch_soft_shift's rule.  u0, x_pred, status, lam_warm and mu (with lam, phi, Cs) are nullable.
+struct AdvanceArgs {
+  int B, N;
+  double dt;
+  double *x, *u, *u0, *x_pred;
+  int* status;
+  const int *exit_code, *iter;   // the solve's per-problem state (ProbState), read when status is set
+  double* lam_warm;
+  const ConstrDev* Cs;
+  double *mu, *lam, *phi;
+};
+int launch_mpc_advance(hipStream_t s, const ModelSel& m, const AdvanceArgs& a);
+
 void launch_soft_shift(hipStream_t s, const ConstrDev* Cs, int B, int N, int nj, double* mu, double* lam,
                        double* phi);
 void launch_outer_init(hipStream_t s, int B, int* outer_active, int* outer_iter, int* exit_soft);

@@ -184,6 +184,7 @@ int alloc_state(tmpc_ctx* ctx, int B, ProbState& st) {
   st.rho = st_rho; st.drho = st_drho; st.J = st_J; st.c = st_c; st.merit = st_merit;
   st.iter = st_iter; st.active = st_active; st.need_grad = st_need; st.exit_sqp = st_exit;
   ctx->last_st = st;
+  ctx->mpc_last.B = 0;   // a solve begins: an MPC step loop continues only where mpc_step_device records it again
   return 0;
 }
 
@@ -836,6 +837,7 @@ int stream_solve(tmpc_ctx* ctx, int N, double dt, int linsys, const tmpc_stream*
   int rc = linsys < 0 ? check_ready(ctx, 1, N, false) : check_ready(ctx, 1, N);
   if (rc) return rc;
   if (!s) return fail(ctx, "null stream");
+  ctx->mpc_last.B = 0;   // (sub-streams solve on contexts of their own: alloc_state of this one may not run)
   if (ctx->ref_R && ctx->hcost.kind == COST_EE)
     return fail(ctx, "a state reference (tmpc_set_reference) with UrdfCost: the task-space goal stays constant; "
                 "clear the reference (tmpc_set_reference with R = 0)");
@@ -908,19 +910,27 @@ int stream_solve(tmpc_ctx* ctx, int N, double dt, int linsys, const tmpc_stream*
 }
 
 // ------------------------------------------------------------------ receding-horizon MPC (oracle/mpc.py)
-int mpc_device(tmpc_ctx* ctx, int B, int N, double dt, int solver, int steps, double* d_x, double* d_u,
-               double* d_xe, double* d_ue, int* d_codes, int* d_iters) {
+// what the MPC loop and its single step refuse
+static int mpc_ready(tmpc_ctx* ctx, int B, int N, int solver) {
   const bool ilqr = solver == TMPC_SOLVER_ILQR;
   int rc = check_ready(ctx, B, N, !ilqr);
   if (rc) return rc;
   if (ctx->hmodel.n > NJ_FULL)
     return fail(ctx, "the MPC loop supports up to %d joints (got %d)", NJ_FULL, ctx->hmodel.n);
   if (ctx->hcost.kind != COST_QUADRATIC) return fail(ctx, "the MPC loop supports QuadraticCost only");
-  if (steps < 1) return fail(ctx, "steps must be >= 1");
   if (!ilqr && precond_of(solver) < 0) return fail(ctx, "solver %d: use TMPC_LINSYS_* or TMPC_SOLVER_ILQR", solver);
   if (!ilqr && ctx->opts.pcg_warm_start && precond_of(solver) != 0 && qp_banded(ctx, N))
     return fail(ctx, "pcg_warm_start with hard box constraints or past the fused QP's rows: the banded PCG takes "
                 "no guess; unset pcg_warm_start");
+  return 0;
+}
+
+int mpc_device(tmpc_ctx* ctx, int B, int N, double dt, int solver, int steps, double* d_x, double* d_u,
+               double* d_xe, double* d_ue, int* d_codes, int* d_iters) {
+  const bool ilqr = solver == TMPC_SOLVER_ILQR;
+  int rc = mpc_ready(ctx, B, N, solver);
+  if (rc) return rc;
+  if (steps < 1) return fail(ctx, "steps must be >= 1");
   const int nj = ctx->hmodel.n, nx = 2 * nj;
   // work counters of the whole loop: the sum over its horizon solves (tmpc_solve_counters)
   int64_t sum_counters[3] = {0, 0, 0};
@@ -965,6 +975,56 @@ int mpc_device(tmpc_ctx* ctx, int B, int N, double dt, int solver, int steps, do
   }
   HIP_OK(hipStreamSynchronize(ctx->stream));
   for (int i = 0; i < 3; ++i) ctx->last_counters[i] = sum_counters[i];
+  return 0;
+}
+
+// One step of the loop above for a caller that closes the loop itself (include/tmpc.h tmpc_mpc_step_device): the
+// measured state into x[:, 0], the horizon solve, then everything mpc_device does between two solves -- the plant
+// step, the status, the shifts of x, u, the warm lambda and the soft constants -- in one launch (k_mpc_advance).
+int mpc_step_device(tmpc_ctx* ctx, int B, int N, double dt, int solver, int step, double* d_x, double* d_u,
+                    const tmpc_mpc_io& io) {
+  const bool ilqr = solver == TMPC_SOLVER_ILQR;
+  int rc = mpc_ready(ctx, B, N, solver);
+  if (rc) return rc;
+  if (!d_x || !d_u) return fail(ctx, "null x/u");
+  if (step < 0) return fail(ctx, "step must be >= 0 (got %d)", step);
+  if (step > 0) {
+    // the warm lambda, the soft constants and QF_start on the device are the previous solve's: they continue
+    // this loop only if that solve was the loop's previous step
+    const auto& l = ctx->mpc_last;
+    if (l.B == 0)
+      return fail(ctx, "MPC step %d: the context's previous solve was not an MPC step (a fresh context, or another "
+                  "solve, stream or configuration change since); expected step 0, which starts a loop", step);
+    if (l.B != B || l.N != N || l.dt != dt || l.solver != solver || l.step != step - 1)
+      return fail(ctx, "MPC step %d (B=%d, N=%d, dt=%g, solver=%d): the context's previous solve was step %d of "
+                  "B=%d, N=%d, dt=%g, solver=%d; expected step %d of that loop, or step 0 to start a new one",
+                  step, B, N, dt, solver, l.step, l.B, l.N, l.dt, l.solver, l.step + 1);
+  }
+  const int nj = ctx->hmodel.n, nx = 2 * nj;
+  if (io.x_meas)   // x[:, 0] <- x_meas, on the stream
+    HIP_OK(hipMemcpy2DAsync(d_x, (size_t)N * sizeof(double), io.x_meas, sizeof(double), sizeof(double), (size_t)B * nx,
+                            hipMemcpyDeviceToDevice, ctx->stream));
+  ctx->ref_step = step;   // a reference slides one column per step (goal_window)
+  rc = ilqr ? ilqr_device(ctx, B, N, dt, d_x, d_u, nullptr)
+            : sqp_device(ctx, B, N, dt, solver, d_x, d_u, nullptr, /*keep_warm=*/step > 0);
+  ctx->ref_step = 0;
+  if (rc) return rc;
+  {
+    Timed t(ctx, "mpc_advance");
+    AdvanceArgs a{};
+    a.B = B; a.N = N; a.dt = dt; a.x = d_x; a.u = d_u; a.u0 = io.u0; a.x_pred = io.x_pred; a.status = io.status;
+    a.exit_code = ctx->last_st.exit_sqp; a.iter = ctx->last_st.iter;
+    if (!ilqr && ctx->opts.pcg_warm_start && precond_of(solver) != 0 && !qp_banded(ctx, N)) a.lam_warm = ctx->lam_warm;
+    if (ctx->hlim.any) { a.Cs = ctx->dlim; a.mu = ctx->soft_mu; a.lam = ctx->soft_lam; a.phi = ctx->soft_phi; }
+    LAUNCH_OK(launch_mpc_advance(ctx->stream, model_sel(ctx), a));
+  }
+  // QuadraticCost.shift_QF_start(-1) (TrajoptCost.py:100-104)
+  if (ctx->hcost.QF_start >= 0) {
+    ctx->hcost.QF_start = ctx->hcost.QF_start > 0 ? ctx->hcost.QF_start - 1 : 0;
+    HIP_OK(hipMemcpyAsync(ctx->dcost, &ctx->hcost, sizeof(CostDev), hipMemcpyHostToDevice, ctx->stream));
+  }
+  HIP_OK(hipStreamSynchronize(ctx->stream));   // the caller reads u0 next
+  ctx->mpc_last = {B, N, solver, step, dt};
   return 0;
 }
 

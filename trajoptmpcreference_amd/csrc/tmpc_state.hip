@@ -54,11 +54,7 @@ __device__ __forceinline__ void reset_outer(int b, int* outer_active, int* outer
   outer_active[b] = 1; outer_iter[b] = 0; exit_soft[b] = 0;
 }
 
-// BoxConstraint.__init__ (:21-24) for a slot of soft type t: mu = mu_init, lambda = 0, phi = phi_init
-struct SoftInit { double mu, lam, phi; };
-__device__ __forceinline__ SoftInit soft_initial(const ConstrDev* __restrict__ Cs, int t) {
-  return {Cs->mu_init[t], 0.0, Cs->phi_init[t]};
-}
+// (soft_initial, the constants a soft slot starts from: tmpc_internal.h, shared with the MPC step's advance kernel)
 
 // the trace row of an iteration (:691-705 / :729-743)
 __device__ __forceinline__ void trace_step_row(const TraceDev& tr, size_t e, int it, int ls, double al, double rho,

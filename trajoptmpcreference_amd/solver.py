@@ -65,6 +65,16 @@ def _method_name(m):
     raise ValueError("Invalid QP Solver options are: N, S, PCG-J, PCG-BJ, PCG-SS")
 
 
+def _mpc_solver_name(m):
+    """An MPCSolverMethods member or its value as the library's solver name: "iLQR" or an SQP method."""
+    m = m.value if isinstance(m, MPCSolverMethods) else str(m)
+    if m == "iLQR":
+        return "iLQR"
+    if m.startswith("QP-") and m[3:] in ("N", "S", "PCG-J", "PCG-BJ", "PCG-SS"):
+        return m[3:]   # QP-N: the dense KKT solve, the Schur complement's solution (method N of SQP)
+    raise NotImplementedError(f"MPC solver {m}: use iLQR, QP-N, QP-S, QP-PCG-J, QP-PCG-BJ or QP-PCG-SS")
+
+
 class TrajoptMPCReference:
     def __init__(self, plantObj: TrajoptPlant, costObj: TrajoptCost, constraintObj: TrajoptConstraint = None):
         if not isinstance(plantObj, TrajoptPlant) or not isinstance(costObj, TrajoptCost):
@@ -155,11 +165,12 @@ class TrajoptMPCReference:
             raise NotImplementedError("goal= runs on the device plugins; a plugin-hook cost sets its own goal")
         return _native.reference_array(goal, np.shape(x)[0], self._dims()[0])
 
-    def _context(self, options, xref=None):
+    def _context(self, options, xref=None, own=False):
         """The plant's context configured for this solver.  xref: the call's reference [R][nx][M] (goal=); else a
         TrackingCost's from its current shift on; else none.  It is set or cleared on every call, and the solver's
         methods clear it again after their solve: the context is shared per device, and a reference left behind
-        would steer the next solve."""
+        would steer the next solve.  own: a new context of the caller's own instead (an MPCSession's, which
+        keeps its configuration and reference for its lifetime)."""
         if self._hooks():
             which = [name for name, ok in (("cost", hooks.device_cost(self.cost) is not None),
                                            ("plant", hooks.device_plant(self.plant)),
@@ -173,8 +184,17 @@ class TrajoptMPCReference:
         spec = self.other_constraints.gpu_spec()   # raises for ADMM_PROJECTION (the reference exits too)
         if options.get("overloading"):
             raise NotImplementedError("overloading (op-history tracing) is instrumentation, not offered")
-        ctx = self.plant._ctx()
+        prec = options.get("precision", "fp64")
+        if prec not in _PRECISION:
+            raise ValueError(f"options['precision'] must be one of {sorted(_PRECISION)}, got {prec!r}")
         c = self.cost
+        if prec != "fp64" and isinstance(c, UrdfCost):
+            raise NotImplementedError("the fp32 / mixed precision modes support QuadraticCost only")
+        if own:
+            ctx = _native.Context(getattr(self.plant, "device", 0))
+            ctx.set_model(self.plant.model, self.plant.options["gravity"])
+        else:
+            ctx = self.plant._ctx()
         if isinstance(c, UrdfCost):
             m = self.plant.model
             ctx.set_cost_ee(c.Q, c.QF, c.R, c.xg, c.QF_start, m.H0[:2], m.Ha[:2], m.Hb[:2])
@@ -182,11 +202,6 @@ class TrajoptMPCReference:
             ctx.set_cost_quadratic(c.Q, c.QF, c.R, c.xg, c.QF_start)
         # pcg_warm_start (build option, default off = the reference): PCG of each QP starts from the
         # previous QP's lambda, across MPC steps from the shifted last lambda (include/tmpc.h)
-        prec = options.get("precision", "fp64")
-        if prec not in _PRECISION:
-            raise ValueError(f"options['precision'] must be one of {sorted(_PRECISION)}, got {prec!r}")
-        if prec != "fp64" and isinstance(c, UrdfCost):
-            raise NotImplementedError("the fp32 / mixed precision modes support QuadraticCost only")
         ctx.set_options(**{v: options[k] for k, v in _OPTION_MAP.items()},
                         pcg_warm_start=int(bool(options.get("pcg_warm_start", False))), precision=_PRECISION[prec])
         ctx.set_box_limits(spec)
@@ -384,13 +399,7 @@ class TrajoptMPCReference:
         loop then never tracked the cost's own reference, and its shift stays."""
         options = {} if options is None else options
         self.set_default_options(options)
-        m = SOLVER_METHOD.value if isinstance(SOLVER_METHOD, MPCSolverMethods) else str(SOLVER_METHOD)
-        if m == "iLQR":
-            solver = "iLQR"
-        elif m.startswith("QP-") and m[3:] in ("N", "S", "PCG-J", "PCG-BJ", "PCG-SS"):
-            solver = m[3:]   # QP-N: the dense KKT solve, the Schur complement's solution (method N of SQP)
-        else:
-            raise NotImplementedError(f"MPC solver {m}: use iLQR, QP-N, QP-S, QP-PCG-J, QP-PCG-BJ or QP-PCG-SS")
+        solver = _mpc_solver_name(SOLVER_METHOD)
         ctx = self._context(options, self._reference(goal, x))
         x = np.asarray(x, dtype=np.float64)
         u = np.asarray(u, dtype=np.float64)
@@ -412,6 +421,14 @@ class TrajoptMPCReference:
         if goal is None and isinstance(self.cost, TrackingCost):
             self.cost.shift_reference(int(mpc_steps))
         return r
+
+    def MPC_session(self, x, u, N: int, dt: float, SOLVER_METHOD=MPCSolverMethods.QP_PCG_SS, options=None,
+                    soft_state=None, goal=None):
+        """The loop of MPC_batch handed to the caller one step at a time, for a controller that runs against a
+        real or simulated plant: returns an MPCSession whose step(x_meas) restarts the horizon from the measured
+        states, solves it and returns the controls to apply.  Arguments as MPC_batch's; stepping a session with
+        no measurement (or with the previous step's x_pred) reproduces MPC_batch bit for bit."""
+        return MPCSession(self, x, u, N, dt, SOLVER_METHOD, options, soft_state, goal)
 
     def MPC(self, x, u, N: int, dt: float, SOLVER_METHOD=MPCSolverMethods.QP_PCG_SS, options=None, mpc_steps: int = 1):
         """One problem: returns (x_exec [nx][steps+1], u_exec [nu][steps], exit_codes, iters)."""
@@ -681,3 +698,135 @@ class TrajoptMPCReference:
                 self.exit_soft = 3
                 exit_flag = True
         return exit_flag, iteration
+
+
+class MPCSession:
+    """A receding-horizon loop for B problems, one step per call (TrajoptMPCReference.MPC_session; the library's
+    tmpc_mpc_step_device).  The session owns a context of its own -- not the plant's per-device one, so other
+    solves on the same solver between two steps leave its warm start (the shifted horizon, the PCG's lambda, the
+    soft-limit constants) alone -- and the device buffers of the horizon and of a step's inputs and outputs.  It
+    keeps its reference (goal=, or a TrackingCost's from its shift at construction on) for its lifetime; per step
+    it moves the host-side mirrors as MPC_batch does per call: cost.QF_start one down (floor 0), a TrackingCost's
+    shift one on unless goal= replaced its reference.  Arguments are checked at construction, x_meas at each step,
+    both before any device work; the context is created and configured, from the solver's cost, constraints and
+    plant as they are then, at the first step.  A context manager: leaving it closes the session."""
+
+    def __init__(self, solver, x, u, N, dt, SOLVER_METHOD=MPCSolverMethods.QP_PCG_SS, options=None, soft_state=None,
+                 goal=None):
+        options = {} if options is None else dict(options)
+        solver.set_default_options(options)
+        self._method = _mpc_solver_name(SOLVER_METHOD)
+        if isinstance(solver.cost, UrdfCost):
+            raise NotImplementedError("the MPC loop supports QuadraticCost only (UrdfCost: solve each horizon "
+                                      "with SQP_batch)")
+        xref = solver._reference(goal, x)
+        if solver._hooks():
+            raise NotImplementedError("an MPC session runs on device plugins only; the cost / plant / constraint "
+                                      "hooks here are the caller's own (the plugin-hook path serves SQP / SQP_batch)")
+        x = np.array(x, dtype=np.float64)
+        u = np.array(u, dtype=np.float64)
+        solver._check_xu(x, u, N)
+        self.B, self.nx, self.nu, self.N, self.dt = x.shape[0], x.shape[1], u.shape[1], int(N), float(dt)
+        con = solver.other_constraints
+        self._soft = None
+        if con.has_any():
+            if con.num_timesteps != N:
+                raise ValueError(f"TrajoptConstraint was built for {con.num_timesteps} knots, solving with N = {N}")
+            if soft_state is None:
+                soft_state = [np.broadcast_to(a, (self.B,) + a.shape) for a in con.pack_state(N)]
+            self._soft = [np.array(a, dtype=np.float64) for a in soft_state]
+            shape = (self.B, self.N, 6 * self.nu)
+            if len(self._soft) != 3 or any(a.shape != shape for a in self._soft):
+                raise ValueError(f"soft_state must be (mu, lam, phi), each {shape}")
+        if xref is None and isinstance(solver.cost, TrackingCost):
+            xref = np.array(solver.cost.window()[None])
+        self._solver, self._options, self._xref, self._own_goal = solver, options, xref, goal is not None
+        self._x, self._u = x, u
+        self._ctx = None
+        self._bufs = {}
+        self._closed = False
+        self.steps_done = 0
+
+    def _open(self):
+        ctx = self._solver._context(self._options, self._xref, own=True)
+        self._ctx = ctx
+        if self._soft is not None:
+            ctx.set_soft_state(self.B, self.N, *self._soft)
+        B, nx, nu = self.B, self.nx, self.nu
+        for name, nbytes in (("x", self._x.nbytes), ("u", self._u.nbytes), ("x_meas", B * nx * 8), ("u0", B * nu * 8),
+                             ("x_pred", B * nx * 8), ("status", B * 2 * 4)):
+            self._bufs[name] = ctx.alloc(nbytes)
+        ctx.h2d(self._bufs["x"], self._x)
+        ctx.h2d(self._bufs["u"], self._u)
+
+    def step(self, x_meas=None):
+        """One step: x[:, 0] <- x_meas ([B][nx]; None: the model's own prediction), the horizon solve, the
+        shift.  Returns dict(u0 [B][nu]: the controls to apply, x_pred [B][nx]: the nominal next states,
+        exit_code [B], iters [B] of this step's solve)."""
+        if self._closed:
+            raise RuntimeError("the MPC session is closed")
+        if x_meas is not None:
+            x_meas = np.ascontiguousarray(x_meas, dtype=np.float64)
+            if x_meas.shape != (self.B, self.nx):
+                raise ValueError(f"x_meas must be [B][nx] = {(self.B, self.nx)}, got {x_meas.shape}")
+        if self._ctx is None:
+            self._open()
+        ctx, d = self._ctx, self._bufs
+        if x_meas is not None:
+            ctx.h2d(d["x_meas"], x_meas)
+        ctx.mpc_step_device(self.B, self.N, self.dt, self._method, self.steps_done, d["x"], d["u"],
+                            d["x_meas"] if x_meas is not None else None, d["u0"], d["x_pred"], d["status"])
+        u0, xp = np.empty((self.B, self.nu)), np.empty((self.B, self.nx))
+        status = np.empty((self.B, 2), dtype=np.int32)
+        ctx.d2h(u0, d["u0"])
+        ctx.d2h(xp, d["x_pred"])
+        ctx.d2h(status, d["status"])
+        self.steps_done += 1
+        cost = self._solver.cost
+        if cost.QF_start is not None:
+            cost.QF_start = max(cost.QF_start - 1, 0)
+        if not self._own_goal and isinstance(cost, TrackingCost):
+            cost.shift_reference(1)
+        return dict(u0=u0, x_pred=xp, exit_code=status[:, 0].copy(), iters=status[:, 1].copy())
+
+    def horizon(self):
+        """The current (shifted) horizon (x [B][nx][N], u [B][nu][N-1]): the next step's warm start."""
+        if self._ctx is not None and not self._closed:
+            self._ctx.d2h(self._x, self._bufs["x"])
+            self._ctx.d2h(self._u, self._bufs["u"])
+        return self._x.copy(), self._u.copy()
+
+    def soft_state(self):
+        """The soft limits' constants (mu, lam, phi), each [B][N][6n], as the next step starts from them; None
+        without soft limits."""
+        if self._soft is None:
+            return None
+        if self._ctx is not None and not self._closed:
+            self._soft = list(self._ctx.get_soft_state(self.B, self.N))
+        return tuple(a.copy() for a in self._soft)
+
+    def close(self):
+        """Frees the device buffers and the context (the last horizon and soft state stay readable)."""
+        if self._closed:
+            return
+        if self._ctx is not None:
+            self.horizon()
+            self.soft_state()
+            for p in self._bufs.values():
+                self._ctx.free(p)
+            self._bufs = {}
+            self._ctx.close()
+        self._closed = True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
