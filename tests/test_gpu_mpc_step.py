@@ -1,10 +1,12 @@
 """GPU: the closed-loop MPC step (tmpc_mpc_step_device, MPCSession).
 
 One call is one iteration of oracle/mpc.py's loop with a measured state injected at its top, so
-  * stepping with no measurement, or with the previous step's x_pred as the measurement, is MPC_batch bit for bit:
-    the horizon solves are the same calls and k_mpc_advance moves the same values k_mpc_shift, the lambda copies
-    and k_soft_shift move (np.array_equal on everything the loop returns, across each 64-knot chunk edge of the
-    shift);
+  * stepping with no measurement, or with the previous step's x_pred as the measurement, is MPC_batch bit for bit
+    (np.array_equal on everything the loop returns).  Both run the same step (mpc_one_step, k_mpc_advance), so
+    this holds the Python mirrors, the x_meas copy, the output addressing of the two callers and the rules of a
+    continued loop;
+  * the shift itself -- x, u and the soft constants across each 64-knot chunk edge of k_mpc_advance -- is the
+    loop restated in NumPy around SQP_batch, again bit for bit;
   * a disturbed measurement steers the solve as it steers the oracle's loop (integers identical, values within
     the existing MPC tests' rtol 1e-6 / atol 1e-8);
   * a step that does not continue the context's previous one is refused with what was expected.
@@ -82,17 +84,65 @@ def test_steps_equal_the_loop(method, variant):
         assert s1.cost.QF_start == 12 - steps
 
 
+def _numpy_loop(solver, x, u, N, opts, x_exec, steps):
+    """oracle/mpc.py's loop around SQP_batch with the shifts in NumPy: without pcg_warm_start, step s of MPC_batch
+    is SQP_batch's solve of the current horizon and soft state.  The plant is not restated: the state after step
+    s is x_exec[:, :, s + 1] of the loop under test (test_gpu_mpc.py holds it against the oracle's).  The soft
+    constants shift as BoxConstraint.shift_soft_constraint_constants(1) does: knot 0 takes knot 1, every later
+    knot of a slot's span returns to (mu_init, 0, phi_init) of the slot's kind; the torque slots (the last 2 n of
+    6 n) span N - 1 knots.  A kind without limits has no constants: its tmpc_box_limits row stays zero
+    (Context.set_box_limits), and its slots, which no solve reads, return to zero."""
+    n = u.shape[1]
+    con = solver.other_constraints
+    init = np.zeros((3, 6 * n))   # (mu, lam, phi) per slot
+    for t, kind in enumerate(con.KINDS):
+        c = getattr(con, kind)
+        if c is not None:
+            init[0, 2 * n * t:2 * n * (t + 1)] = c.options["quadratic_penalty_mu_init"]
+            init[2, 2 * n * t:2 * n * (t + 1)] = c.options["augmentated_lagrangian_phi_init"]
+    span = np.array([N] * 4 * n + [N - 1] * 2 * n)
+    x, u, soft = x.copy(), u.copy(), None
+    u_exec, codes, iters = [], [], []
+    for s in range(steps):
+        r = solver.SQP_batch(x, u, N, DT, "PCG-SS", dict(opts), soft_state=soft)
+        x, u, soft = r["x"].copy(), r["u"].copy(), [a.copy() for a in r["soft_state"]]
+        u_exec.append(u[:, :, 0].copy())
+        codes.append(r["exit_sqp"])
+        iters.append(r["sqp_iter"])
+        x[..., :-1] = x[..., 1:].copy()
+        x[..., 0] = x_exec[:, :, s + 1]
+        u[..., :-1] = u[..., 1:].copy()
+        for a, a0 in zip(soft, init):
+            a[:, 0] = a[:, 1]
+            for k in range(1, N):
+                a[:, k, k < span] = a0[k < span]
+    return dict(x=x, u=u, soft_state=soft, u_exec=np.stack(u_exec, axis=2), exit_codes=np.stack(codes, axis=1),
+                iters=np.stack(iters, axis=1))
+
+
 @pytest.mark.parametrize("N", [3, 64, 65, 66, 129, 130])
 def test_chunked_shift_across_the_chunk_edges(N):
     """k_mpc_advance shifts 64 knots per chunk: one knot either side of each chunk edge (N - 1 = 63 .. 65 and
     128, 129 shifted knots) and the smallest horizon, with every array the kernel moves in play -- x, u, the warm
-    lambda, the soft constants (torque rows: N - 1 knots).  arm2 at N = 130 is 520 Schur rows: the fused QP."""
+    lambda, the soft constants (torque rows: N - 1 knots).  arm2 at N = 130 is 520 Schur rows: the fused QP.
+    Two statements: the session's steps are the loop's with the warm lambda in play (the output addressing of both
+    callers), and, with a cold PCG, the loop is SQP_batch with the shifts restated in NumPy (the shift itself;
+    the warm lambda has no accessor and is not part of this one)."""
     B, steps = 2, 2
     x, u = _problems("arm2", N, B, 740)
     opts = {"max_iter_SQP_DDP": 2, "max_iter_softConstraints": 2, "pcg_warm_start": True}
     spec = {"torque": ([-0.7] * 2, [0.7] * 2, "AUGMENTED_LAGRANGIAN")}
     r = _setup(2, N, spec=spec).MPC_batch(x, u, N, DT, "QP-PCG-SS", dict(opts), mpc_steps=steps)
     _assert_is_the_loop(*_run_session(_setup(2, N, spec=spec), x, u, N, "QP-PCG-SS", opts, steps), r)
+
+    cold = {k: v for k, v in opts.items() if k != "pcg_warm_start"}
+    r = _setup(2, N, spec=spec).MPC_batch(x, u, N, DT, "QP-PCG-SS", dict(cold), mpc_steps=steps)
+    assert np.array_equal(r["x_exec"][:, :, 0], x[:, :, 0])
+    e = _numpy_loop(_setup(2, N, spec=spec), x, u, N, cold, r["x_exec"], steps)
+    for key in ("u_exec", "exit_codes", "iters", "x", "u"):
+        assert np.array_equal(r[key], e[key]), key
+    for a, b in zip(r["soft_state"], e["soft_state"]):
+        assert np.array_equal(a, b)
 
 
 # ---------------------------------------------------------------------------------------------- measurements

@@ -2,18 +2,20 @@
 """Latency of the closed-loop MPC step against the on-device loop.
 
 Workload: arm6, N = 64, QP-PCG-SS, fp64, pcg_warm_start, max_iter_SQP_DDP = 4, B problems resident in HBM,
-`--steps` MPC steps from the same start every repeat.  Two ways through the same horizon solves:
+`--steps` MPC steps from the same start every repeat.  Two ways through the same horizon solves and the same
+k_mpc_advance launch between them:
   step   `--steps` calls of tmpc_mpc_step_device, each measuring x_meas = the previous call's x_pred (so the
-         results are the loop's), one host synchronisation per call, one k_mpc_advance launch between solves;
-  batch  one tmpc_mpc_batch_device(steps), the loop on the device: k_mpc_shift, the lambda and status copies.
+         results are the loop's): the x_meas copy and one host synchronisation per call;
+  batch  one tmpc_mpc_batch_device(steps), the loop on the device, one synchronisation at its end.
 Per B: a warm-up of each, then `--repeats` timed repeats, the two modes alternating; a host clock around the whole
 loop, which ends in a device synchronisation.  Reported per mode: per-step median, min, max and spread
-(max - min) in ms.  A last pass with the library's launch timing on (options.profile) reports the average time
-of the kernels that differ: mpc_shift (batch) and mpc_advance (step).
+(max - min) in ms.  A last pass with the library's launch timing on (options.profile) reports per mode the
+average time of the launch between two solves, "mode:name": the library times it as mpc_shift.
 
 --package-root DIR runs the package and library of another checkout (built there) -- the parent commit's, whose
-loop is the yardstick; a checkout without the step entry point runs --modes batch.  Reads nothing else outside
-the repository; prints one JSON line per batch size and, with --out, writes them to a file."""
+loop is the yardstick; a checkout without the step entry point runs --modes batch, and one from before the two
+modes shared their kernel times its step under the name mpc_advance.  Reads nothing else outside the repository;
+prints one JSON line per batch size and, with --out, writes them to a file."""
 import argparse
 import json
 import os
@@ -105,7 +107,7 @@ def main(argv=None):
             for name in ("mpc_shift", "mpc_advance"):
                 cnt, ms = ctx.kernel_stats(name)
                 if cnt:
-                    kernels[name] = dict(launches=cnt, avg_ms=ms / cnt)
+                    kernels[f"{m}:{name}"] = dict(launches=cnt, avg_ms=ms / cnt)
         line["kernels"] = kernels
         ctx.set_options(profile=0)
         for p in d.values():

@@ -303,66 +303,22 @@ __global__ void __launch_bounds__(64) k_rollout(MT M, PList P, int B, int N, dou
   }
 }
 
-// ======================================================================= MPC step (oracle/mpc.py)
-// One 64-lane workgroup per problem after a horizon solve: apply the first
-// control to the plant, x_next = integrator(x_0, u_0) (TrajoptPlant.py:92-99),
-// record it, and shift the trajectory by one knot for the warm start
-// (x_k <- x_{k+1}, u_k <- u_{k+1}, last knot kept, x_0 <- x_next).
-template <int NJ, bool CHAIN, class MT>
-__global__ void __launch_bounds__(64) k_mpc_shift(MT M, int B, int N, double dt, int step, int steps,
-                                                  double* __restrict__ x, double* __restrict__ u,
-                                                  double* __restrict__ xe, double* __restrict__ ue) {
-  constexpr int NX = 2 * NJ, NU = NJ;
-  const int b = blockIdx.x, t = threadIdx.x;
-  const int K = N - 1;
-  double* xb = x + (size_t)b * NX * N;
-  double* ub = u + (size_t)b * NU * K;
-  __shared__ double xn[NX];
-  if (t == 0) {
-    // the simulated plant is fp64 in every precision mode
-    double q[NJ], qd[NJ], uu[NJ], qdd[NJ], cq[NJ], sq[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      q[j] = xb[j * N];
-      qd[j] = xb[(NJ + j) * N];
-      uu[j] = ub[j * K];
-      joint_cs(M, j, q[j], cq[j], sq[j]);
-    }
-    fd_aba<NJ, CHAIN>(M, cq, sq, qd, uu, qdd);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      xn[j] = __dadd_rn(q[j], __dmul_rn(dt, qd[j]));
-      xn[NJ + j] = __dadd_rn(qd[j], __dmul_rn(dt, qdd[j]));
-    }
-#pragma unroll
-    for (int m = 0; m < NX; ++m) xe[((size_t)b * NX + m) * (steps + 1) + step + 1] = xn[m];
-#pragma unroll
-    for (int m = 0; m < NU; ++m) ue[((size_t)b * NU + m) * steps + step] = uu[m];
-  }
-  __syncthreads();
-  // shift each state / control row (rows are contiguous in the [nx][N] layout)
-  for (int m = t; m < NX; m += 64) {
-    double* row = xb + m * N;
-    for (int k = 0; k < N - 1; ++k) row[k] = row[k + 1];
-    row[0] = xn[m];
-  }
-  for (int m = t; m < NU; m += 64) {
-    double* row = ub + m * K;
-    for (int k = 0; k < K - 1; ++k) row[k] = row[k + 1];
-  }
-}
-
-// ======================================================================= MPC step, handed back (tmpc_mpc_step_device)
-// Everything the loop does between two horizon solves, for a caller that closes the loop itself: one 64-lane
-// workgroup per problem.  Lane 0 takes the Euler step with k_mpc_shift's operation sequence (the bits of x_pred are
-// the loop's x_exec) while lane 1 copies the solve's status; then the lanes spread along the knots, 64 per chunk.
-// A row shifts in place, so a chunk's last lane reads the element the next chunk's first lane writes (64 c + 64):
-// every lane loads its knot k + 1 of all rows -- x, u and the warm lambda's block, which shifts by the same
-// rule -- into registers, the workgroup meets at a barrier, then every lane stores to knot k.  Chunks ascend, so
-// a chunk's stores (knots < 64 c + 64) never reach what a later chunk still has to load (knots > 64 c + 64).
-// The soft constants follow k_soft_shift's rule: knot 0 takes knot 1's value and every later knot of the slot's
-// span (torque limits: N - 1 knots) returns to soft_initial; lane sl < 6 NJ holds slot sl's knot-1 values over
-// the barrier while all lanes write the constants, 64 consecutive elements per pass.
+// ======================================================================= MPC advance (oracle/mpc.py, AdvanceArgs)
+// Everything the MPC loop does between two horizon solves, one 64-lane workgroup per problem.  Lane 0 applies the
+// first control to the plant, x_next = integrator(x_0, u_0) (TrajoptPlant.py:92-99): joint_cs and fd_aba in fp64,
+// then q + dt qd and qd + dt qdd as one __dmul_rn and one __dadd_rn each (no contraction: the executed states
+// are the same bits wherever the step runs), while lane 1 copies the solve's status; then the lanes spread along
+// the knots, 64 per chunk, for the warm start's shift (x_k <- x_{k+1}, u_k <- u_{k+1}, last knot kept,
+// x_0 <- x_next).  A row shifts in place, so a chunk's last lane reads the element the next chunk's first lane
+// writes (64 c + 64): every lane loads its knot k + 1 of all rows -- x, u and the warm lambda's block, which
+// shifts by the same rule -- into registers, the workgroup meets at a barrier, then every lane stores to knot k.
+// Chunks ascend, so a chunk's stores (knots < 64 c + 64) never reach what a later chunk still has to load
+// (knots > 64 c + 64).
+// The soft constants: BoxConstraint.shift_soft_constraint_constants(1) (TrajoptConstraint.py:168-176) on the
+// [B][N][6n] state, arr[:, :-1] = arr[:, 1:]; arr[:, 1:] = init (the reference's semantics: knot 0 takes knot
+// 1's value and every later knot of the slot's span returns to soft_initial; torque limits span N - 1 knots).
+// Lane sl < 6 NJ holds slot sl's knot-1 values over the barrier while all lanes write the constants, 64
+// consecutive elements per pass.
 template <int NJ, bool CHAIN, class MT>
 __global__ void __launch_bounds__(64) k_mpc_advance(MT M, AdvanceArgs a) {
   constexpr int NX = 2 * NJ, NU = NJ, MC = 6 * NJ;
@@ -388,18 +344,18 @@ __global__ void __launch_bounds__(64) k_mpc_advance(MT M, AdvanceArgs a) {
       xn[j] = __dadd_rn(q[j], __dmul_rn(a.dt, qd[j]));
       xn[NJ + j] = __dadd_rn(qd[j], __dmul_rn(a.dt, qdd[j]));
     }
-    if (a.x_pred) {
+    if (a.x_out) {
 #pragma unroll
-      for (int m = 0; m < NX; ++m) a.x_pred[(size_t)b * NX + m] = xn[m];
+      for (int m = 0; m < NX; ++m) a.x_out[((size_t)b * NX + m) * a.x_ld] = xn[m];
     }
-    if (a.u0) {
+    if (a.u_out) {
 #pragma unroll
-      for (int m = 0; m < NU; ++m) a.u0[(size_t)b * NU + m] = uu[m];
+      for (int m = 0; m < NU; ++m) a.u_out[((size_t)b * NU + m) * a.u_ld] = uu[m];
     }
   }
-  if (t == 1 && a.status) {
-    a.status[2 * b] = a.exit_code[b];
-    a.status[2 * b + 1] = a.iter[b];
+  if (t == 1) {
+    if (a.code_out) a.code_out[(size_t)b * a.st_ld] = a.exit_code[b];
+    if (a.iter_out) a.iter_out[(size_t)b * a.st_ld] = a.iter[b];
   }
   __syncthreads();
   double* lw = a.lam_warm ? a.lam_warm + (size_t)b * N * NX : nullptr;
@@ -495,10 +451,6 @@ struct LaunchFD {
                          a.u, a.xnext, a.qdd);
     });
   }
-  static void mpc_shift(hipStream_t s, const ModelDev* M, const ShiftArgs& a) {
-    hipLaunchKernelGGL((k_mpc_shift<NJ, CHAIN, MT>), dim3(a.B), dim3(64), 0, s, MT::make(M), a.B, a.N, a.dt, a.step,
-                       a.steps, a.x, a.u, a.xe, a.ue);
-  }
   // (the MPC entry points refuse a wide model: no instance)
   static void mpc_advance(hipStream_t s, const ModelDev* M, const AdvanceArgs& a) {
     if constexpr (!kWide<NJ>)
@@ -545,13 +497,6 @@ int launch_rollout(bool f32, hipStream_t s, const ModelSel& m, const Batch& b, d
   return dispatch_model(m.mid, m.nj, m.chain, [&](auto t) {
     using T = decltype(t);
     LaunchFD<T::nj, T::chain, typename T::model>::rollout(f32, s, m.M, b, dt, x, u, mask);
-  });
-}
-
-int launch_mpc_shift(hipStream_t s, const ModelSel& m, const ShiftArgs& a) {
-  return dispatch_model(m.mid, m.nj, m.chain, [&](auto t) {
-    using T = decltype(t);
-    LaunchFD<T::nj, T::chain, typename T::model>::mpc_shift(s, m.M, a);
   });
 }
 

@@ -290,40 +290,39 @@ int launch_ilqr_forward_trk(bool f32, hipStream_t s, const ModelSel& m, const Il
 int launch_ilqr_init_cost_trk(hipStream_t s, int nj, const IlqrArgs& a);
 
 void launch_ilqr_decide(hipStream_t s, const DecideArgs& a);
-// the MPC step: x_0, u_0 through the plant into xe / ue [.. ][steps (+ 1)], the trajectory shifted by one knot
-struct ShiftArgs {
-  int B, N;
-  double dt;
-  int step, steps;
-  double *x, *u, *xe, *ue;
-};
-int launch_mpc_shift(hipStream_t s, const ModelSel& m, const ShiftArgs& a);
-
 // BoxConstraint.__init__ (:21-24) for a slot of soft type t: mu = mu_init, lambda = 0, phi = phi_init
 struct SoftInit { double mu, lam, phi; };
 __device__ __forceinline__ SoftInit soft_initial(const ConstrDev* __restrict__ Cs, int t) {
   return {Cs->mu_init[t], 0.0, Cs->phi_init[t]};
 }
 
-// One step of the MPC loop handed back to the caller (tmpc_mpc_step_device), everything between two horizon solves
-// in one launch: x_0, u_0 through the plant into x_pred / u0 [B][nx] / [B][nu] (launch_mpc_shift's operations), the
-// solve's exit code and iterations into status [B][2], the trajectory shifted by one knot with x_0 = x_pred, the PCG
-// warm start lam_warm [B][N][nx] shifted by one block (last kept), the soft constants mu / lam / phi [B][N][6 nj]
-// shifted by launch_soft_shift's rule.  u0, x_pred, status, lam_warm and mu (with lam, phi, Cs) are nullable.
+// Everything between two horizon solves of the MPC loop (oracle/mpc.py), in one launch per step:
+//   * the plant: x_next = x_0 + dt * (qd_0, qdd(x_0, u_0)), nominal explicit Euler in fp64 (TrajoptPlant.py:92-99),
+//     each component one __dmul_rn and one __dadd_rn; x_next and u_0 go to x_out / u_out, the solve's exit code
+//     and iteration count to code_out / iter_out;
+//   * the trajectory shifted by one knot: x_k <- x_{k+1}, u_k <- u_{k+1}, last knot kept, x_0 <- x_next;
+//   * the PCG warm start lam_warm [B][N][nx] shifted by one block, last block kept;
+//   * the soft constants mu / lam / phi [B][N][6 nj] as BoxConstraint.shift_soft_constraint_constants(1) shifts
+//     them (TrajoptConstraint.py:168-176): arr[:, :-1] = arr[:, 1:]; arr[:, 1:] = init -- knot 0 takes knot 1's
+//     value and every later knot of the slot's span returns to soft_initial; torque rows span N - 1 knots.
+// An output row is (problem, component) for the doubles and the problem for the ints; *_ld is the element stride
+// between consecutive rows, so one kernel writes a step's own arrays (tmpc_mpc_step_device: ld 1, status ld 2)
+// and a column of the loop's (tmpc_mpc_batch: x_exec [B][nx][steps + 1], u_exec [B][nu][steps], codes / iters
+// [B][steps]).  x_out, u_out, code_out, iter_out, lam_warm and mu (with lam, phi, Cs) are nullable.
 struct AdvanceArgs {
   int B, N;
   double dt;
-  double *x, *u, *u0, *x_pred;
-  int* status;
-  const int *exit_code, *iter;   // the solve's per-problem state (ProbState), read when status is set
+  double *x, *u;
+  double* x_out; size_t x_ld;
+  double* u_out; size_t u_ld;
+  int *code_out, *iter_out; size_t st_ld;
+  const int *exit_code, *iter;   // the solve's per-problem state (ProbState), read when code_out / iter_out is set
   double* lam_warm;
   const ConstrDev* Cs;
   double *mu, *lam, *phi;
 };
 int launch_mpc_advance(hipStream_t s, const ModelSel& m, const AdvanceArgs& a);
 
-void launch_soft_shift(hipStream_t s, const ConstrDev* Cs, int B, int N, int nj, double* mu, double* lam,
-                       double* phi);
 void launch_outer_init(hipStream_t s, int B, int* outer_active, int* outer_iter, int* exit_soft);
 void launch_soft_init(hipStream_t s, const ConstrDev* Cs, size_t total, int MC, double* mu, double* lam,
                       double* phi);

@@ -925,53 +925,62 @@ static int mpc_ready(tmpc_ctx* ctx, int B, int N, int solver) {
   return 0;
 }
 
+// where one step's outputs go (AdvanceArgs: first element and row stride of each; all nullable)
+struct MpcStepOut {
+  double* x_next; size_t x_ld;
+  double* u0; size_t u_ld;
+  int *code, *iters; size_t st_ld;
+};
+
+// One iteration of oracle/mpc.py's loop on the stream: the horizon solve of step `step`, then everything between
+// two solves in one launch (k_mpc_advance: the plant step and the status into `out`, the shifts of x, u, the warm
+// lambda and the soft constants) and QF_start one down.  No synchronisation of its own beyond the solve's.
+static int mpc_one_step(tmpc_ctx* ctx, int B, int N, double dt, int solver, int step, double* d_x, double* d_u,
+                        const MpcStepOut& out) {
+  const bool ilqr = solver == TMPC_SOLVER_ILQR;
+  ctx->ref_step = step;   // a reference slides one column per step (goal_window)
+  int rc = ilqr ? ilqr_device(ctx, B, N, dt, d_x, d_u, nullptr)
+                : sqp_device(ctx, B, N, dt, solver, d_x, d_u, nullptr, /*keep_warm=*/step > 0);
+  ctx->ref_step = 0;
+  if (rc) return rc;
+  {
+    Timed t(ctx, "mpc_shift");
+    AdvanceArgs a{};
+    a.B = B; a.N = N; a.dt = dt; a.x = d_x; a.u = d_u;
+    a.x_out = out.x_next; a.x_ld = out.x_ld; a.u_out = out.u0; a.u_ld = out.u_ld;
+    a.code_out = out.code; a.iter_out = out.iters; a.st_ld = out.st_ld;
+    a.exit_code = ctx->last_st.exit_sqp; a.iter = ctx->last_st.iter;
+    // the next step's first PCG starts from this step's last lambda shifted by one knot (oracle/mpc.py)
+    if (!ilqr && ctx->opts.pcg_warm_start && precond_of(solver) != 0 && !qp_banded(ctx, N)) a.lam_warm = ctx->lam_warm;
+    if (ctx->hlim.any) { a.Cs = ctx->dlim; a.mu = ctx->soft_mu; a.lam = ctx->soft_lam; a.phi = ctx->soft_phi; }
+    LAUNCH_OK(launch_mpc_advance(ctx->stream, model_sel(ctx), a));
+  }
+  // QuadraticCost.shift_QF_start(-1) (TrajoptCost.py:100-104)
+  if (ctx->hcost.QF_start >= 0) {
+    ctx->hcost.QF_start = ctx->hcost.QF_start > 0 ? ctx->hcost.QF_start - 1 : 0;
+    HIP_OK(hipMemcpyAsync(ctx->dcost, &ctx->hcost, sizeof(CostDev), hipMemcpyHostToDevice, ctx->stream));
+  }
+  return 0;
+}
+
 int mpc_device(tmpc_ctx* ctx, int B, int N, double dt, int solver, int steps, double* d_x, double* d_u,
                double* d_xe, double* d_ue, int* d_codes, int* d_iters) {
-  const bool ilqr = solver == TMPC_SOLVER_ILQR;
   int rc = mpc_ready(ctx, B, N, solver);
   if (rc) return rc;
   if (steps < 1) return fail(ctx, "steps must be >= 1");
-  const int nj = ctx->hmodel.n, nx = 2 * nj;
+  const int nx = 2 * ctx->hmodel.n;
   // work counters of the whole loop: the sum over its horizon solves (tmpc_solve_counters)
   int64_t sum_counters[3] = {0, 0, 0};
   // executed state 0 = x[:, 0]
   HIP_OK(hipMemcpy2DAsync(d_xe, (size_t)(steps + 1) * sizeof(double), d_x, (size_t)N * sizeof(double), sizeof(double),
                           (size_t)B * nx, hipMemcpyDeviceToDevice, ctx->stream));
-  for (int s = 0; s < steps; ++s) {
-    ctx->ref_step = s;   // a reference slides one column per step (goal_window)
-    rc = ilqr ? ilqr_device(ctx, B, N, dt, d_x, d_u, nullptr)
-              : sqp_device(ctx, B, N, dt, solver, d_x, d_u, nullptr, /*keep_warm=*/s > 0);
-    ctx->ref_step = 0;
+  auto col = [](auto* p, int c) { return p ? p + c : p; };   // (a null output stays null)
+  for (int s = 0; s < steps; ++s) {   // step s fills column s + 1 of x_exec and column s of u_exec, codes, iters
+    const size_t ld = (size_t)steps;
+    rc = mpc_one_step(ctx, B, N, dt, solver, s, d_x, d_u,
+                      {d_xe + s + 1, ld + 1, col(d_ue, s), ld, col(d_codes, s), col(d_iters, s), ld});
     if (rc) return rc;
     for (int i = 0; i < 3; ++i) sum_counters[i] += ctx->last_counters[i];
-    if (!ilqr && ctx->opts.pcg_warm_start && precond_of(solver) != 0 && !qp_banded(ctx, N)) {
-      // the next step's first PCG starts from this step's last lambda shifted by one knot
-      // (lambda_k <- lambda_{k+1}, last block kept), as x and u are shifted (oracle/mpc.py)
-      double* lw = ctx->lam_warm;
-      BUF(double, lam_tmp, (size_t)B * N * nx);
-      const size_t row = (size_t)N * nx * sizeof(double), blk = (size_t)nx * sizeof(double);
-      HIP_OK(hipMemcpyAsync(lam_tmp, lw, (size_t)B * row, hipMemcpyDeviceToDevice, ctx->stream));
-      HIP_OK(hipMemcpy2DAsync(lw, row, (char*)lam_tmp + blk, row, row - blk, B, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    HIP_OK(hipMemcpy2DAsync(d_codes + s, (size_t)steps * sizeof(int), ctx->last_st.exit_sqp, sizeof(int),
-                            sizeof(int), B, hipMemcpyDeviceToDevice, ctx->stream));
-    HIP_OK(hipMemcpy2DAsync(d_iters + s, (size_t)steps * sizeof(int), ctx->last_st.iter, sizeof(int),
-                            sizeof(int), B, hipMemcpyDeviceToDevice, ctx->stream));
-    {
-      Timed t(ctx, "mpc_shift");
-      ShiftArgs a{};
-      a.B = B; a.N = N; a.dt = dt; a.step = s; a.steps = steps; a.x = d_x; a.u = d_u; a.xe = d_xe; a.ue = d_ue;
-      LAUNCH_OK(launch_mpc_shift(ctx->stream, model_sel(ctx), a));
-    }
-    // QuadraticCost.shift_QF_start(-1) (TrajoptCost.py:100-104)
-    if (ctx->hcost.QF_start >= 0) {
-      ctx->hcost.QF_start = ctx->hcost.QF_start > 0 ? ctx->hcost.QF_start - 1 : 0;
-      HIP_OK(hipMemcpyAsync(ctx->dcost, &ctx->hcost, sizeof(CostDev), hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (ctx->hlim.any) {
-      launch_soft_shift(ctx->stream, ctx->dlim, B, N, nj, ctx->soft_mu, ctx->soft_lam, ctx->soft_phi);
-      HIP_OK(hipGetLastError());
-    }
   }
   HIP_OK(hipStreamSynchronize(ctx->stream));
   for (int i = 0; i < 3; ++i) ctx->last_counters[i] = sum_counters[i];
@@ -979,11 +988,9 @@ int mpc_device(tmpc_ctx* ctx, int B, int N, double dt, int solver, int steps, do
 }
 
 // One step of the loop above for a caller that closes the loop itself (include/tmpc.h tmpc_mpc_step_device): the
-// measured state into x[:, 0], the horizon solve, then everything mpc_device does between two solves -- the plant
-// step, the status, the shifts of x, u, the warm lambda and the soft constants -- in one launch (k_mpc_advance).
+// measured state into x[:, 0], then the loop's step.
 int mpc_step_device(tmpc_ctx* ctx, int B, int N, double dt, int solver, int step, double* d_x, double* d_u,
                     const tmpc_mpc_io& io) {
-  const bool ilqr = solver == TMPC_SOLVER_ILQR;
   int rc = mpc_ready(ctx, B, N, solver);
   if (rc) return rc;
   if (!d_x || !d_u) return fail(ctx, "null x/u");
@@ -1000,29 +1007,13 @@ int mpc_step_device(tmpc_ctx* ctx, int B, int N, double dt, int solver, int step
                   "B=%d, N=%d, dt=%g, solver=%d; expected step %d of that loop, or step 0 to start a new one",
                   step, B, N, dt, solver, l.step, l.B, l.N, l.dt, l.solver, l.step + 1);
   }
-  const int nj = ctx->hmodel.n, nx = 2 * nj;
+  const int nx = 2 * ctx->hmodel.n;
   if (io.x_meas)   // x[:, 0] <- x_meas, on the stream
     HIP_OK(hipMemcpy2DAsync(d_x, (size_t)N * sizeof(double), io.x_meas, sizeof(double), sizeof(double), (size_t)B * nx,
                             hipMemcpyDeviceToDevice, ctx->stream));
-  ctx->ref_step = step;   // a reference slides one column per step (goal_window)
-  rc = ilqr ? ilqr_device(ctx, B, N, dt, d_x, d_u, nullptr)
-            : sqp_device(ctx, B, N, dt, solver, d_x, d_u, nullptr, /*keep_warm=*/step > 0);
-  ctx->ref_step = 0;
+  rc = mpc_one_step(ctx, B, N, dt, solver, step, d_x, d_u,
+                    {io.x_pred, 1, io.u0, 1, io.status, io.status ? io.status + 1 : nullptr, 2});
   if (rc) return rc;
-  {
-    Timed t(ctx, "mpc_advance");
-    AdvanceArgs a{};
-    a.B = B; a.N = N; a.dt = dt; a.x = d_x; a.u = d_u; a.u0 = io.u0; a.x_pred = io.x_pred; a.status = io.status;
-    a.exit_code = ctx->last_st.exit_sqp; a.iter = ctx->last_st.iter;
-    if (!ilqr && ctx->opts.pcg_warm_start && precond_of(solver) != 0 && !qp_banded(ctx, N)) a.lam_warm = ctx->lam_warm;
-    if (ctx->hlim.any) { a.Cs = ctx->dlim; a.mu = ctx->soft_mu; a.lam = ctx->soft_lam; a.phi = ctx->soft_phi; }
-    LAUNCH_OK(launch_mpc_advance(ctx->stream, model_sel(ctx), a));
-  }
-  // QuadraticCost.shift_QF_start(-1) (TrajoptCost.py:100-104)
-  if (ctx->hcost.QF_start >= 0) {
-    ctx->hcost.QF_start = ctx->hcost.QF_start > 0 ? ctx->hcost.QF_start - 1 : 0;
-    HIP_OK(hipMemcpyAsync(ctx->dcost, &ctx->hcost, sizeof(CostDev), hipMemcpyHostToDevice, ctx->stream));
-  }
   HIP_OK(hipStreamSynchronize(ctx->stream));   // the caller reads u0 next
   ctx->mpc_last = {B, N, solver, step, dt};
   return 0;
