@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE ONLY (imported by tests/, never by the product): a restatement of the dense PCG
-of tmpc_pcg_dense_batch (csrc/tmpc_hard.hip: k_pcg_dense, k_dense_gj, k_dense_stair) in its own
+of tmpc_pcg_dense_batch (csrc/tmpc_pcg_dense.hip: k_pcg_dense, k_dense_gj, k_dense_stair) in its own
 operation order, so the GPU can be checked bit for bit on identical inputs.
 
 GBD-PCG-Python/PCG.py:66-111 (PCG.pcg(A, b, Pinv, guess, options)): any dense A and preconditioner

@@ -354,6 +354,114 @@ def test_hard_qp_matches_oracle_at_every_iterate(name, N, method, spec):
         assert e_got <= 100 * e_ref + 1e-9 * sc, (i, e_got, e_ref)
 
 
+def _mixed_oracle(method, seed, n, N):
+    """One oracle SQP pass of arm3 with soft torque limits (AUGMENTED_LAGRANGIAN, +-0.3) and hard velocity limits
+    (ACTIVE_SET, +-0.6), the soft state the initial one throughout (one outer pass), with the statements that
+    make the case a test of the per-knot Ghat branch asserted on the oracle alone."""
+    from oracle import hard as ohard
+    from oracle import sqp as osqp
+    from oracle.soft import SoftConstraints, SoftLimit
+    m = arm_model("arm3")
+    nx = 2 * n
+
+    def soft():   # the initial soft state (sqp updates its argument in place)
+        return SoftConstraints([SoftLimit("torque", n, N, [-0.3] * n, [0.3] * n, "AUGMENTED_LAGRANGIAN")])
+
+    hard = ohard.HardConstraints([ohard.HardLimit("velocity", n, -0.6, 0.6, "ACTIVE_SET")])
+    cost = osqp.QuadCost(*quad_cost_arrays(n))
+    x0, u0 = osqp.initial_problem(m, N, 0.1, seed)
+    opts = {"max_iter_softConstraints": 1}
+    o = osqp.sqp(m, cost, x0, u0, N, 0.1, method, dict(opts), soft(), hard=hard, order="canonical")
+    its = o["iterates"]
+    assert len(its) == len(o["dxul"]) == 5 and o["outer_iter"] <= 1
+    assert not any(o["singular"])
+    fresh = soft()
+    for i in range(1, 5):   # QPs 1-4: hard rows and soft terms together
+        x, u, _ = its[i]
+        assert any(o["active_masks"][i]), i
+        assert any(np.any(np.asarray(j) != 0) for k in range(N - 1)
+                   for j in fresh.jacobians(x[:, k], u[:, k], k, N, nx + n)), i
+    if method.startswith("PCG"):
+        assert len(o["pcg_iters"]) == 5
+        assert max(o["pcg_iters"]) < osqp.default_options(opts)["max_iter_linSys"]
+    return m, hard, fresh, cost, x0, u0, opts, o
+
+
+@pytest.mark.parametrize("seed", (400, 401))
+@pytest.mark.parametrize("method", ("S", "PCG-SS"))
+def test_hard_qp_with_soft_limits_matches_oracle(method, seed):
+    """The banded QP with soft limits present: k_hard_schur and k_hard_dxu read the per-knot Ghat blocks
+    (G_k + soft jacobian terms + rho I)^-1 from HBM, and the gradient carries the soft jacobians.  The five QPs of
+    one oracle SQP pass (arm3, N = 8; soft torque limits, hard velocity limits), batched on the GPU as in
+    test_hard_qp_matches_oracle_at_every_iterate, with that test's assertions at its tolerances: active masks and
+    the Schur dimension identical; S and gamma against the dense formation at 1e-10 relative; method S: dxul
+    against the dense solve at 1e-9; PCG-SS: the canonical-order PCG on the GPU's own S / gamma takes the GPU's
+    count exactly and returns its lambda bit for bit.  (Measured when the test was added, before k_hard_schur's
+    row loop was rewritten: S within 3.0e-15, gamma 1.4e-15, dxu 7.5e-12, lambda 1.5e-12; PCG counts 13-44.)"""
+    from oracle import hard as ohard
+    from oracle import sqp as osqp
+    from trajoptmpcreference_amd import QuadraticCost, TrajoptConstraint, TrajoptMPCReference, URDFPlant, planar_arm_urdf
+    n, N = 3, 8
+    nx = 2 * n
+    m, hard, soft, cost, x0, u0, opts, o = _mixed_oracle(method, seed, n, N)
+    its = o["iterates"]
+    B = len(its)
+    con = TrajoptConstraint(n, n, n, N)
+    _hard_spec(con, n, {"torque": (-0.3, 0.3, "AUGMENTED_LAGRANGIAN"), "velocity": (-0.6, 0.6, "ACTIVE_SET")})
+    solver = TrajoptMPCReference(URDFPlant(options={"path_to_urdf": planar_arm_urdf(n)}),
+                                 QuadraticCost(*quad_cost_arrays(n)), con)
+    full = dict(opts)
+    solver.set_default_options(full)
+    ctx = solver._context(full)
+    ctx.set_soft_state(B, N)   # the initial soft state, whatever an earlier solve of this shape left
+    xs = np.array([x for x, _, _ in its])
+    us = np.array([u for _, u, _ in its])
+    rho = np.array([r for _, _, r in its])
+    r = ctx.qp_batch(xs, us, N, 0.1, rho, method, want_blocks=False, xs=np.repeat(x0[:, 0][None], B, 0))
+    info = ctx.qp_hard_info(B, N)
+    W = info["W"]
+    nz = (nx + n) * (N - 1) + nx
+    o_opts = osqp.default_options(opts)
+    for i, (x, u, rho_i) in enumerate(its):
+        assert [int(v) for v in info["active"][i]] == o["active_masks"][i], i
+        dyn, hrows = _row_layout(hard, x, u, N, nx)
+        G, g, Cm, cc = ohard.kkt_dense(m, cost, x, u, x0[:, 0], N, 0.1, hard, soft)
+        D = Cm.shape[0]
+        assert int(info["dim"][i]) == D, i
+        invG = np.linalg.inv(G + rho_i * np.eye(G.shape[0]))
+        S_o = -Cm @ (invG @ Cm.T)
+        gam_o = cc - Cm @ (invG @ g)
+        S_g = _unband(info["S_band"][i], W, D)
+        gam_g = info["gamma"][i, :D]
+        e_S = float(np.max(np.abs(S_g - S_o))) / float(np.max(np.abs(S_o)))
+        e_gam = float(np.max(np.abs(gam_g - gam_o))) / max(1.0, float(np.max(np.abs(gam_o))))
+        print(f"mixed {method} seed {seed} QP {i}: D {D} S {e_S:.3e} gamma {e_gam:.3e}")
+        assert e_S <= 1e-10, i
+        assert e_gam <= 1e-10, i
+        got = r["dxul"][i]
+        lam_dyn = got[nz:]
+        lam_hard = np.array([info["lambda_hard"][i, k, sl] for _, k, sl in hrows])
+        ha = [a for a, _, _ in hrows]
+        if method == "S":
+            ref = o["dxul"][i]
+            assert bool(info["singular"][i]) == o["singular"][i], i
+            sc = max(1.0, float(np.max(np.abs(ref[:nz]))))
+            sl = max(1.0, float(np.max(np.abs(ref[nz:]))))
+            e_dxu = float(np.max(np.abs(got[:nz] - ref[:nz]))) / sc
+            e_lam = max(float(np.max(np.abs(lam_dyn - ref[nz:][dyn]))),
+                        float(np.max(np.abs(lam_hard - ref[nz:][ha]), initial=0.0))) / sl
+            print(f"mixed S seed {seed} QP {i}: dxu {e_dxu:.3e} lambda {e_lam:.3e}")
+            assert e_dxu < 1e-9, i
+            assert e_lam < 1e-9, i
+            continue
+        lam_c, it_c = ohard.pcg_canonical(S_g, gam_g, nx, method[4:], o_opts["exit_tolerance_linSys"],
+                                          o_opts["max_iter_linSys"])
+        print(f"mixed {method} seed {seed} QP {i}: pcg {int(r['pcg_iters'][i])} canonical {it_c}")
+        assert int(r["pcg_iters"][i]) == it_c, (i, int(r["pcg_iters"][i]), it_c)
+        assert np.array_equal(lam_dyn, lam_c[dyn]), i
+        assert np.array_equal(lam_hard, lam_c[ha]), i
+
+
 PCG_CASES = [("arm3", 12, "BJ", 400), ("arm3", 12, "SS", 400), ("arm3", 12, "J", 401), ("arm2", 16, "0", 430)]
 
 

@@ -588,7 +588,7 @@ int tmpc_hard_pcg_batch(tmpc_ctx* ctx, int B, int nx, int dmax, int W, const int
   std::vector<int> ones(B, 1);
   HIP_OK(hipMemcpyAsync(hp_act, ones.data(), sizeof(int) * B, hipMemcpyHostToDevice, ctx->stream));
   HardArgs h{};
-  h.B = B; h.phase = 1; h.precond = precond; h.dmax = dmax; h.W = W; h.tol = tol; h.max_iter = max_iter;
+  h.B = B; h.precond = precond; h.dmax = dmax; h.W = W; h.tol = tol; h.max_iter = max_iter;
   h.active = hp_act; h.dim = hp_dim; h.Sb = hp_Sb; h.gam = hp_gam; h.Pd = hp_Pd; h.Pl = hp_Pl; h.Ptr = hp_Ptr;
   h.lam = hp_lam; h.iters = hp_it; h.rng = hp_rng;
   int rc;
@@ -597,7 +597,7 @@ int tmpc_hard_pcg_batch(tmpc_ctx* ctx, int B, int nx, int dmax, int W, const int
   h.work = hp_work;
   {
     Timed t(ctx, "hard_pcg");
-    LAUNCH_OK(launch_hard(ctx->stream, nx / 2, h));
+    LAUNCH_OK(launch_hard_solve(ctx->stream, nx / 2, h));
   }
   if ((rc = collect_hard_work(ctx, h))) return rc;
   resolve_timings(ctx);

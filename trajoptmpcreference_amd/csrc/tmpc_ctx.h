@@ -303,7 +303,7 @@ int init_soft(tmpc_ctx* ctx, int B, int N, bool fresh, Work* w);
 int setup_hard(tmpc_ctx* ctx, int B, int N, int T, int precond, HardArgs& hard, int nj_given = -1,
                int rmax_given = -1);
 int collect_hard_work(tmpc_ctx* ctx, const HardArgs& hard);
-int run_hard_qp(tmpc_ctx* ctx, int nj, HardArgs& h);
+int run_hard_qp(tmpc_ctx* ctx, int nj, const HardArgs& h);
 // the horizon, step, trajectory and st's masks into w's blocks: once per solve, before run_qp / ilqr_sweeps
 void bind_work(const tmpc_ctx* ctx, int N, double dt, const double* d_x, const double* d_u, const ProbState& st,
                Work& w);

@@ -232,7 +232,7 @@ struct DecideArgs : Batch {
   int mode, soft;
   const double *terms, *dx, *du;
   const int* pcg_iters;
-  const double* hterms;     // hard limits: the violation terms of launch_hard phase 3 (else null)
+  const double* hterms;     // hard limits: the violation terms of launch_hard_ls (else null)
   const int* qp_singular;   // HardArgs.sing of the direct banded solve (else null)
   // launch_ilqr_decide
   int init;
@@ -327,36 +327,59 @@ void launch_outer_init(hipStream_t s, int B, int* outer_active, int* outer_iter,
 void launch_soft_init(hipStream_t s, const ConstrDev* Cs, size_t total, int MC, double* mu, double* lam,
                       double* phi);
 
-// Hard box constraints (tmpc_hard.hip): one argument block for its four launch phases
-// (0 rows + layout + Schur band, 1 PCG / direct solve, 2 dxu, 3 line-search terms).
+// The banded QP (tmpc_hard.hip: hard box constraints, the QP past QP_MAX_ROWS rows, the plugin-hook QP's banded
+// path): one block for its launchers, grouped by the launchers that read a field.
 struct HardArgs {
-  int B, N, T, phase, precond, rmax, dmax, W, per_knot, max_iter;
-  double tol;
-  const ConstrDev* Cs;
-  const CostDev* C;
-  const double *x, *u, *Ghat, *A, *Bm, *cvec, *jsoft, *alphas;
+  // every launcher
+  int B, N;
   const int* active;
-  int *cnt, *hcol, *roff, *hoff, *dim, *rkind, *rknot, *ridx, *PK, *iters;
-  double *hsgn, *hval, *Y, *Sb, *gam, *Pd, *Pl, *Ptr, *M, *rhs, *lam, *dx, *du, *hterms;
-  int* hslot;                     // [B][N][rmax] t * 2n + e of each row
-  unsigned long long* amask;      // [B][N] active-set bitmask per knot (bit t * 2n + e)
-  int* sing;                      // [B] the direct solve took the least-squares answer (singular S)
+  // launch_hard_schur, launch_hard_solve, launch_hard_dxu: the knots' rows, the row layout, S lam = gam
+  int rmax, dmax, W;              // rows per knot and Schur rows at most; the band's half-width
+  int *cnt, *hcol;                // [B][N] rows of each knot; [B][N][rmax] each row's column of [x_k; u_k]
+  int *roff, *hoff, *dim;         // [B][N] first row of R_j, of H_k; [B] the Schur dimension (launch_hard_schur writes)
+  double *hsgn, *Sb, *gam, *lam;  // [B][N][rmax] the rows' signs; [B][2W+1][dmax] row-start-relative band; [B][dmax] each
   int* rng;                       // [B][dmax][2] first / last structurally nonzero column of each row of S
-  const int* iter;                // per-problem SQP iteration (trace row iter + 1)
-  int Wtr;                        // trace row stride (max_iter_SQP_DDP + 1)
-  unsigned long long* tr_active;  // [B][Wtr][N] trace copy of amask (nullable)
-  double* work;                   // [B] algorithmic HBM bytes of k_hard_pcg, accumulated per problem (nullable)
+  // launch_hard_schur, launch_hard_dxu (launch_hard_track_grad: C, x, u, jsoft; launch_hard_ls: x, u)
+  const CostDev* C;
+  const double *x, *u, *Ghat, *A, *Bm, *jsoft;
+  int per_knot;                   // Ghat: 0 [B][3][nx nx] (k_ginv), 1 per knot (soft limits, k_ginv_soft), 2 below
   // the plugin-hook QP (tmpc_qp_blocks_banded_batch): per_knot = 2 -- Ghat holds full (G_k + rho I)^-1 blocks
   // [B][N][nx+nu][nx+nu] -- the caller's cost gradient gvec [B][N][nx+nu] (null: the context's cost), and
   // rows_given: cnt / hcol / hsgn / hval were filled from the caller's constraint hooks (k_hard_rows skipped)
   const double* gvec;
   int rows_given;
+  // launch_hard_schur only
+  const ConstrDev* Cs;            // launch_hard_ls too
+  const double* cvec;
+  double *hval, *Y;               // [B][N][rmax] the rows' values; scratch [B][2][nx+nu][dmax], Ghat times the rows' pieces
+  int *rkind, *rknot, *ridx;      // [B][dmax] per row: dynamics / hard, knot, index (k_hard_layout)
+  int* hslot;                     // [B][N][rmax] t * 2n + e of each row
+  unsigned long long* amask;      // [B][N] active-set bitmask per knot (bit t * 2n + e)
+  const int* iter;                // per-problem SQP iteration (trace row iter + 1)
+  int Wtr;                        // trace row stride (max_iter_SQP_DDP + 1)
+  unsigned long long* tr_active;  // [B][Wtr][N] trace copy of amask (nullable)
+  // launch_hard_solve only: precond 0 the banded elimination (M, rhs, sing), else the PCG
+  int precond, max_iter;
+  double tol;
+  int* iters;
+  double *Pd, *Pl, *Ptr, *M, *rhs;   // the PCG's preconditioner blocks past its LDS cache; the elimination's S and gam
+  double* work;                   // [B] algorithmic HBM bytes of k_hard_pcg, accumulated per problem (nullable)
+  int* sing;                      // [B] the direct solve took the least-squares answer (singular S)
+  // launch_hard_dxu (writes), launch_hard_ls (reads: the trial points x - alpha dx, u - alpha du; null: x, u)
+  double *dx, *du;
+  // launch_hard_ls only
+  int T;
+  const double* alphas;           // [T]
+  double* hterms;                 // [B][T][N]
 };
 // k_hard_pcg: 1024 threads per problem, row a on thread a % 1024 (row slot a / 1024, at most 4 slots)
 constexpr int HARD_PCG_THREADS = 1024, HARD_PCG_MAX_SLOTS = 4;
 constexpr int HARD_PCG_MAX_ROWS = HARD_PCG_THREADS * HARD_PCG_MAX_SLOTS;
 constexpr int HARD_PCG_LDS_BYTES = 160 * 1024;   // all of a CU's LDS: vectors + preconditioner-block cache
-int launch_hard(hipStream_t s, int nj, const HardArgs& h);
+int launch_hard_schur(hipStream_t s, int nj, const HardArgs& h);
+int launch_hard_solve(hipStream_t s, int nj, const HardArgs& h);
+int launch_hard_dxu(hipStream_t s, int nj, const HardArgs& h);
+int launch_hard_ls(hipStream_t s, int nj, const HardArgs& h);
 // the banded QP's cost gradient against the goal window gw (hard_grad's expressions with gw[b][k] for xg), into
 // gvec [B][N][nx+nu]: HardArgs.gvec of a tracking solve, so k_hard_schur / k_hard_dxu run unchanged
 int launch_hard_track_grad(hipStream_t s, int nj, const HardArgs& h, const double* gw, double* gvec);
@@ -370,7 +393,7 @@ inline size_t hard_schur_lds_bytes(int N, int nj, int dmax) {
 constexpr size_t CU_LDS_BYTES = 160 * 1024;   // gfx950: 160 KB of LDS per CU
 int hard_set_max_lds();
 
-// the dense PCG of tmpc_pcg_dense_batch (tmpc_hard.hip): PCG.pcg with any A / Pinv, D <= HARD_PCG_MAX_ROWS.
+// the dense PCG of tmpc_pcg_dense_batch (tmpc_pcg_dense.hip): PCG.pcg with any A / Pinv, D <= HARD_PCG_MAX_ROWS.
 // A row-major [B][D][D] (the preconditioner builders read it), AT / PT column-major (A^T, Pinv^T: the PCG
 // reads columns), Pd [B][D / nx][nx][nx] the builders' diagonal blocks
 struct DenseArgs {

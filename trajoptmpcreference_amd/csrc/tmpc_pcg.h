@@ -57,6 +57,53 @@ __device__ __forceinline__ double perm_pair_sum32(double v) {
   return __hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1]);
 }
 
+// ---- workgroup sum (deterministic): wave DPP butterfly via shuffles + fixed-order fan-in
+// Double-buffered form for a sequence of sums (k_hard_pcg): sum number k uses slots red[16 (k & 1) ..],
+// so the barrier that protects a slot set from being overwritten while a slow wave still reads it is
+// the NEXT sum's own barrier -- one barrier per sum instead of two.
+// The 64-lane xor butterfly v += v[l ^ off] for off = 32, 16, 8, 4, 2, 1 (oracle/hard.py _dot) on the
+// VALU: permlane swaps (32, 16), DPP row_ror:8, row_shl:4 / row_shr:4 picked by lane bit 2, quad_perm
+// (2, 1).  Each step adds the same two values as the shuffle form (addition commutes), so the sums
+// are bitwise those of __shfl_xor, without its six ds_bpermute round trips through the LDS unit.
+__device__ __forceinline__ double h_wave_butterfly(double v) {
+  v = perm_pair_sum32(v);
+  v = perm_pair_sum16(v);
+  v += dpp_get<0x128, 0xf>(v);   // row_ror:8: lane l reads l ^ 8
+  {
+    const double up = dpp_get<0x104, 0xf>(v);   // row_shl:4: lane l reads l + 4 (lanes with bit 2 clear)
+    const double dn = dpp_get<0x114, 0xf>(v);   // row_shr:4: lane l reads l - 4 (bit 2 set)
+    v += (threadIdx.x & 4) ? dn : up;
+  }
+  v += dpp_get<0x4E, 0xf>(v);    // quad_perm [2,3,0,1]: l ^ 2
+  v += dpp_get<0xB1, 0xf>(v);    // quad_perm [1,0,3,2]: l ^ 1
+  return v;
+}
+
+// (k_hard_pcg's HARD_PCG_THREADS workgroup: the fan-in over its 16 waves unrolled)
+__device__ __forceinline__ double h_block_sum_db(double v, double* red, int& k) {
+  constexpr int NW = HARD_PCG_THREADS / 64;
+  v = h_wave_butterfly(v);
+  const int w = threadIdx.x >> 6;
+  double* rs = red + 16 * (k & 1);
+  ++k;
+  if ((threadIdx.x & 63) == 0) rs[w] = v;
+  __syncthreads();
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < NW; ++i) s += rs[i];
+  return s;
+}
+__device__ __forceinline__ double h_block_sum(double v, double* red) {
+  v = h_wave_butterfly(v);
+  const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[w] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int i = 0; i < nw; ++i) s += red[i];
+  return s;
+}
+
 // wave64 sum in every lane: row sums R_q by DPP, then (R0 + R1) + (R2 + R3) by the
 // two permlane swaps -- the tree of the row_bcast:15 / row_bcast:31 reduction, so
 // bitwise the same total, without the readlane round trip through SGPRs.  (Both

@@ -49,14 +49,11 @@ void bind_work(const tmpc_ctx* ctx, int N, double dt, const double* d_x, const d
   w.qp.C = w.gs.C = ctx->dcost; w.gs.Cs = ctx->dlim;
 }
 
-// the banded QP's three phases: rows + layout + Schur band, the solve, dxu
-int run_hard_qp(tmpc_ctx* ctx, int nj, HardArgs& h) {
-  const char* names[3] = {"hard_schur", h.precond == 0 ? "hard_direct" : "hard_pcg", "dxu"};
-  for (int ph = 0; ph < 3; ++ph) {
-    Timed t(ctx, names[ph]);
-    h.phase = ph;
-    LAUNCH_OK(launch_hard(ctx->stream, nj, h));
-  }
+// the banded QP: rows + layout + Schur band, the solve, dxu
+int run_hard_qp(tmpc_ctx* ctx, int nj, const HardArgs& h) {
+  { Timed t(ctx, "hard_schur"); LAUNCH_OK(launch_hard_schur(ctx->stream, nj, h)); }
+  { Timed t(ctx, h.precond == 0 ? "hard_direct" : "hard_pcg"); LAUNCH_OK(launch_hard_solve(ctx->stream, nj, h)); }
+  { Timed t(ctx, "dxu"); LAUNCH_OK(launch_hard_dxu(ctx->stream, nj, h)); }
   return 0;
 }
 
@@ -300,7 +297,6 @@ int setup_hard(tmpc_ctx* ctx, int B, int N, int T, int precond, HardArgs& hard, 
   BUF(int, hd_rkind, (size_t)B * hard.dmax);
   BUF(int, hd_rknot, (size_t)B * hard.dmax);
   BUF(int, hd_ridx, (size_t)B * hard.dmax);
-  BUF(int, hd_pk, (size_t)B * hard.dmax * 2);
   BUF(int, hd_slot, (size_t)B * N * rbuf);
   BUF(unsigned long long, hd_amask, (size_t)B * N);
   BUF(int, hd_sing, (size_t)B);
@@ -314,7 +310,7 @@ int setup_hard(tmpc_ctx* ctx, int B, int N, int T, int precond, HardArgs& hard, 
   BUF(double, hd_lam, (size_t)B * hard.dmax);
   hard.cnt = hd_cnt; hard.hcol = hd_col; hard.hsgn = hd_sgn; hard.hval = hd_val;
   hard.roff = hd_roff; hard.hoff = hd_hoff; hard.dim = hd_dim;
-  hard.rkind = hd_rkind; hard.rknot = hd_rknot; hard.ridx = hd_ridx; hard.PK = hd_pk;
+  hard.rkind = hd_rkind; hard.rknot = hd_rknot; hard.ridx = hd_ridx;
   hard.Y = hd_Y; hard.Sb = hd_Sb; hard.gam = hd_gam; hard.lam = hd_lam;
   ctx->hard_dev = hard;   // what tmpc_qp_hard_info reads once a QP has run on them (hard_last)
   if (precond == 0) {
@@ -354,9 +350,8 @@ int collect_hard_work(tmpc_ctx* ctx, const HardArgs& hard) {
 static int hard_ls(tmpc_ctx* ctx, int nj, const HardArgs& base, int B, int N, int T, const double* alphas, const double* x,
                    const double* u, double* dx, double* du, const int* active) {
   HardArgs h = base;
-  h.phase = 3; h.B = B; h.N = N; h.T = T; h.alphas = alphas; h.x = x; h.u = u; h.dx = dx; h.du = du;
-  h.active = active;
-  return launch_hard(ctx->stream, nj, h);
+  h.B = B; h.N = N; h.T = T; h.alphas = alphas; h.x = x; h.u = u; h.dx = dx; h.du = du; h.active = active;
+  return launch_hard_ls(ctx->stream, nj, h);
 }
 
 // The problem list of the lock-step loop: mask = the per-problem "may still do work" flag (st.active
