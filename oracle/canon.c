@@ -2,7 +2,7 @@
  *
  * PCG.pcg / PCG.compute_preconditioner (GBD-PCG-Python/PCG.py:66-111, :166-212) on a
  * block-tridiagonal S, restated in ONE canonical operation order: the order of the GPU's
- * fused QP kernel (k_qp / k_pcg, csrc/tmpc_kernels.hip pcg_precondition / pcg_run), so that on
+ * fused QP kernel (k_qp / k_pcg, csrc/tmpc_qp.hip, csrc/tmpc_pcg.h pcg_precondition / pcg_run), so that on
  * the same S and gamma the iteration count and lambda agree bit for bit.
  * Compiled with -ffp-contract=off: every fused multiply-add below is an explicit fma() (the
  * kernel's contracted updates), every other product and sum is rounded on its own.

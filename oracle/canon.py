@@ -11,7 +11,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 PRECOND = {"J": 1, "BJ": 2, "SS": 3, "0": 4}
-# the kernel's layout thresholds (csrc/tmpc_kernels.hip pcg_rpl, LaunchNJ::qp; csrc/tmpc_internal.h)
+# the kernel's layout thresholds (csrc/tmpc_pcg.h pcg_rpl, csrc/tmpc_qp.hip qp_geom; csrc/tmpc_internal.h)
 RPL1_MAX_ROWS = 768
 REG_MAX_ROWS = 1024
 
@@ -40,7 +40,7 @@ def _p(a):
 
 
 def qp_rpl(N, nx, gm_min_rows=None):
-    """Rows of S per lane of the fused QP kernel's PCG for an N-block system (LaunchNJ::qp): the GM
+    """Rows of S per lane of the fused QP kernel's PCG for an N-block system (qp_geom in PCG mode): the GM
     instance (past 1024 rows, or from `gm_min_rows` rows when TMPC_QP_GM_MIN_ROWS forces it) and the
     register instance past 768 rows take two; otherwise one."""
     rows = N * nx

@@ -1,6 +1,6 @@
 // Stand-alone check of csrc/tmpc_dispatch.h (tests/test_host_dispatch.py compiles and runs it with the host
 // compiler's address / undefined-behaviour sanitizers): the table from runtime (model id, joint count, chain,
-// precision) to template arguments, on three fake compiled models and a recording callable.
+// precision, QP mode and flags) to template arguments, on three fake compiled models and a recording callable.
 #include <cstdio>
 #include <type_traits>
 #include <vector>
@@ -135,11 +135,50 @@ static void check_with_real() {
   static_assert(!kWide<NJ_FULL> && kWide<NJ_FULL + 1>, "the wide joint counts start past NJ_FULL");
 }
 
+// with_bool / with_qp_mode: a runtime value reaches its one candidate, EVERY all of them in the tables' order
+static void check_with_bool() {
+  for (int v : {0, 1, 5, EVERY}) {
+    std::vector<int> seen;
+    with_bool(v, [&](auto b) { seen.push_back(decltype(b)::value ? 1 : 0); });
+    if (v == EVERY) CHECK(seen == std::vector<int>({1, 0}));   // true first
+    else CHECK(seen == std::vector<int>({v != 0 ? 1 : 0}));
+    // an axis without `true` instances: a clear flag and EVERY reach `false` alone, a set flag nothing
+    seen.clear();
+    with_bool<false>(v, [&](auto b) {
+      static_assert(!decltype(b)::value, "with_bool<false> names no true instance");
+      seen.push_back(0);
+    });
+    CHECK(seen == (v > 0 ? std::vector<int>() : std::vector<int>({0})));
+  }
+}
+
+static void check_with_qp_mode() {
+  static_assert(QP_MODE_PCG == 0 && QP_MODE_SCHUR == 1 && QP_MODE_DXU == 2, "QpArgs::mode values");
+  for (int mode : {-7, EVERY, 0, 1, 2, 3}) {
+    std::vector<int> seen;
+    with_qp_mode(mode, [&](auto m) { seen.push_back(decltype(m)::value); });
+    if (mode == EVERY) CHECK(seen == std::vector<int>({QP_MODE_PCG, QP_MODE_SCHUR, QP_MODE_DXU}));
+    else if (mode >= 0 && mode <= 2) CHECK(seen == std::vector<int>({mode}));
+    else CHECK(seen.empty());   // no such mode: no instance
+  }
+  // the axes nest: every (mode, flag) pair exactly once, and a launch's pair alone
+  int pairs[3][2] = {};
+  with_qp_mode(EVERY, [&](auto m) { with_bool(EVERY, [&](auto b) { ++pairs[decltype(m)::value][decltype(b)::value]; }); });
+  for (auto& row : pairs) CHECK(row[0] == 1 && row[1] == 1);
+  int hits = 0;
+  with_qp_mode(QP_MODE_SCHUR, [&](auto m) {
+    with_bool(1, [&](auto b) { hits += decltype(m)::value == QP_MODE_SCHUR && decltype(b)::value; });
+  });
+  CHECK(hits == 1);
+}
+
 int main() {
   check_runtime_table();
   check_compiled_models();
   check_for_nj();
   check_with_real();
+  check_with_bool();
+  check_with_qp_mode();
   if (failures) {
     printf("%d check(s) failed\n", failures);
     return 1;

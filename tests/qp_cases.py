@@ -147,7 +147,7 @@ DENSE = ("dense", "qfstart-dense")
 def groups_of(key):
     """the groups of one model: horizons 2, 3, 8 x costs default, identity, dense with the three rho as a Latin
     square (ilqr_cases.groups_of), both QF_start costs, B = 1 once (arm3), B = 65 with mixed rho (arm3, arm6,
-    arm12: 195 matrices, not a multiple of the 4 or 2 a wave of k_ginv / k_ginv_wide holds), the soft groups"""
+    arm12: 195 matrices, not a multiple of the 4 or 2 a wave of k_ginv holds at 16 or 32 lanes per matrix), the soft groups"""
     grid = [(N, c) for N in (2, 3, 8) for c in ("default", "identity", "dense")]
     gs = [Group(key, N, c, "none", 8, 600, RHOS[(i + i // 3) % 3]) for i, (N, c) in enumerate(grid)]
     gs += [Group(key, 8, "qfstart", "none", 8, 620, 1e-3), Group(key, 8, "qfstart-dense", "none", 8, 621, 1.0)]

@@ -372,3 +372,74 @@ def test_plugin_qp_past_1024_rows(method):
     assert np.max(np.abs(lam - lam_c)) < 1e-9 * max(1.0, np.max(np.abs(lam_c)))
     # the primal step from lambda: within the PCG's tolerance of the exact KKT solution
     assert np.max(np.abs(got[:nz] - ref[:nz])) < 1e-3 * max(1.0, np.max(np.abs(ref[:nz])))
+
+
+def _two_row_blocks():
+    """Synthetic plugin blocks at nx = 14, nu = 7, N = 55: 770 Schur rows, the smallest even-nx shape past the 768
+    rows of the one-row-per-lane instance.  B = 2.  G_k SPD with an x-u cross term, A_k = I + a small dense
+    perturbation, B_k, g, c dense."""
+    rng = np.random.default_rng(55)
+    nu, N, B = 7, 55, 2
+    nx, n = 2 * nu, 3 * nu
+    G = np.zeros((B, N, n, n))
+    for b in range(B):
+        for k in range(N):
+            m = n if k < N - 1 else nx
+            M = rng.uniform(-1.0, 1.0, (m, m))
+            G[b, k, :m, :m] = M @ M.T / m + np.eye(m)   # dense: the x-u cross block is M_x M_u^T / m
+    g = rng.uniform(-1.0, 1.0, (B, N, n))
+    g[:, N - 1, nx:] = 0.0
+    A = rng.uniform(-0.05, 0.05, (B, N - 1, nx, nx)) + np.eye(nx)
+    Bm = rng.uniform(-0.1, 0.1, (B, N - 1, nx, nu))
+    c = rng.uniform(-0.1, 0.1, (B, N, nx))
+    rho = np.array([1e-3, 0.5])
+    return G, g, A, Bm, c, rho
+
+
+def test_plugin_qp_two_rows_per_lane():
+    """k_qp_blocks' two-rows-per-lane instance (769..1024 Schur rows with even nx; every other plugin-QP test
+    stays below 768 rows) on synthetic blocks of 770 rows, two problems with different rho:
+      * S_diag / S_lo / gamma of method PCG-SS are bit for bit those of method S (one prologue, run in PCG and
+        in SCHUR mode);
+      * the canonical-order PCG (oracle/canon.c, two rows per lane) on that S takes the GPU's count and gives
+        its lambda bit for bit -- the counts (checked on the CPU when the shape was chosen: well below
+        max_iter_linSys) end by the tolerance;
+      * method S's dxul solves the dense KKT system of the same blocks: residual below 1e-8 max(1, max|rhs|),
+        the bound of test_plugin_qp_level_methods."""
+    from oracle import canon
+    from trajoptmpcreference_amd import _native
+    G, g, A, Bm, c, rho = _two_row_blocks()
+    B, N, n, _ = G.shape
+    nx, nu = A.shape[2], Bm.shape[3]
+    assert N * nx == 770 and canon.qp_rpl(N, nx) == 2
+    ctx = _native.default_context(0)
+    tol, max_iter = ctx.options.exit_tolerance_linSys, ctx.options.max_iter_linSys
+    p = ctx.qp_blocks_batch(G, g, A, Bm, c, rho, "PCG-SS", want_blocks=True)
+    s = ctx.qp_blocks_batch(G, g, A, Bm, c, rho, "S", want_blocks=True)
+    for key in ("S_diag", "S_lo", "gamma"):
+        assert np.array_equal(p[key], s[key]), key
+    nz = n * (N - 1) + nx
+    for b in range(B):
+        lam, it, _ = canon.pcg(p["S_diag"][b], p["S_lo"][b], p["gamma"][b], "SS", tol=tol, max_iter=max_iter, rpl=2)
+        print(f"problem {b}: rho {rho[b]:g}, PCG-SS iterations GPU {int(p['pcg_iters'][b])} canonical {it}")
+        assert it == int(p["pcg_iters"][b]), (b, it, int(p["pcg_iters"][b]))
+        assert it < max_iter, (b, it)   # ended by the tolerance (37 and 38 of 100 when the shape was chosen)
+        assert np.array_equal(lam, p["dxul"][b][-N * nx:]), b
+        # the dense KKT system of the blocks (formKKTSystemBlocks :200-271, rho on G's diagonal :319-322)
+        Gd = np.zeros((nz, nz))
+        gd = np.zeros(nz)
+        C = np.zeros((nx * N, nz))
+        C[:nx, :nx] = np.eye(nx)
+        for k in range(N):
+            m = n if k < N - 1 else nx
+            Gd[k * n:k * n + m, k * n:k * n + m] = G[b, k, :m, :m]
+            gd[k * n:k * n + m] = g[b, k, :m]
+            if k < N - 1:
+                C[(k + 1) * nx:(k + 2) * nx, k * n:k * n + nx] = -A[b, k]
+                C[(k + 1) * nx:(k + 2) * nx, k * n + nx:k * n + n] = -Bm[b, k]
+                C[(k + 1) * nx:(k + 2) * nx, (k + 1) * n:(k + 1) * n + nx] = np.eye(nx)
+        K = np.block([[Gd + rho[b] * np.eye(nz), C.T], [C, np.zeros((nx * N, nx * N))]])
+        rhs = np.concatenate([gd, c[b].reshape(-1)])
+        res = float(np.max(np.abs(K @ s["dxul"][b] - rhs)))
+        print(f"problem {b}: method S KKT residual {res:.3e}")
+        assert res < 1e-8 * max(1.0, float(np.max(np.abs(rhs)))), (b, res)

@@ -1,4 +1,4 @@
-"""Unit parity of the QP kernels (k_ginv, k_ginv_wide, k_ginv_soft, k_qp's prologue qp_schur_row, its
+"""Unit parity of the QP kernels (k_ginv at 16 and at 32 lanes per matrix, k_ginv_soft, k_qp's prologue qp_schur_row, its
 preconditioner, PCG and epilogue, k_btsolve) through tmpc_qp_batch and tmpc_qp_last_inputs, which reads back what
 the QP consumed: A, Bm, c and the per-knot Ghat.  Inputs: tests/qp_cases.py (conditioned and shown to be
 sensitive on the CPU by test_oracle_qp_hp.py): dense costs, non-zero goals, QF_start with dense QF != Q, 1..12
@@ -34,7 +34,7 @@ MEASURED on the MI355X, largest err_gpu / (err_cpu64 + floor / 8), every group w
                  Ghat   S     gamma  P     dxu   direct residual
   one row        1.6    2.0   2.0    3.4   2.7   4.4      (1..7 joints and the tree, N = 2, 3, 8, no soft limits)
   soft           1.9    1.6   1.8    2.5   2.0   4.2      (k_ginv_soft, both limit sets)
-  wide           1.3    1.3   2.4    3.6   1.7   3.4      (arm8, arm12: k_ginv_wide)
+  wide           1.3    1.3   2.4    3.6   1.7   3.4      (arm8, arm12: k_ginv at 32 lanes per matrix)
   two rows       1.5    1.1   1.2    1.3   1.8   -        (arm7 N = 55, arm12 N = 33)
   GM forced      0.83   0.81  1.2    0.64  1.6   -        (arm3 N = 8, arm1 N = 2)
   GM natural     1.1    1.1   1.5    0.8   0.78  -        (arm6 N = 86)

@@ -1,5 +1,5 @@
-"""The launchers' table from runtime (model id, joint count, chain, precision) to template arguments
-(csrc/tmpc_dispatch.h: for_nj, for_each_nj, for_model, with_real) in a stand-alone program
+"""The launchers' table from runtime (model id, joint count, chain, precision, QP mode and flags) to template
+arguments (csrc/tmpc_dispatch.h: for_nj, for_each_nj, for_model, with_real, with_bool, with_qp_mode) in a stand-alone program
 (host_dispatch_check.cpp, its own main, three fake compiled models) built with the host compiler's address and
 undefined-behaviour sanitizers.  No GPU, nothing loaded into Python."""
 import os

@@ -67,6 +67,12 @@ struct CostDev {            // QuadraticCost (TrajoptCost.py:24-104) or UrdfCost
   double eeH0[2][16], eeHa[2][16], eeHb[2][16];
 };
 
+// the state block of knot k is QF: the terminal knot and from QF_start on (QuadraticCost.get_currQ,
+// TrajoptCost.py:40-47)
+__device__ __forceinline__ bool use_QF(const CostDev* C, int k, int N) {
+  return (k == N - 1) || (C->QF_start >= 0 && k >= C->QF_start);
+}
+
 // sum_c M[r][c] y[c] for a diagonal M of order n (CostDev.diag): the generic chain's value.
 // poison: NaN when some y[c] is non-finite and n > 1 (then 0 * y[c] enters every generic row sum
 // but the diagonal one), else 0 -- callers add it to the result the generic form would have poisoned

@@ -1,4 +1,4 @@
-// The one place that maps runtime (model id, joint count, chain, precision) to template arguments.
+// The one place that maps runtime (model id, joint count, chain, precision, QP mode and flags) to template arguments.
 // Every launcher picks its kernel instance through these; adding a joint count or a compiled model
 // changes this table (and the model list of tmpc_models.h), not the launchers.
 // Host-only and free of HIP headers: tests/host_dispatch_check.cpp builds it with a plain C++ compiler.
@@ -87,6 +87,32 @@ void with_real(bool f32, F&& f) {
     }
   }
   f(double{});
+}
+
+// The instance tables of the QP kernels (tmpc_qp.hip for_qp, tmpc_hooks.hip for_qp_blocks) walk their template
+// axes with the two helpers below.  A launch passes each axis its runtime value and reaches one instance; the
+// set_max_lds lists pass EVERY and reach all of them -- one table, so neither can name an instance the other lacks.
+constexpr int EVERY = -1;
+
+// f(std::true_type{}) for a set flag v, f(std::false_type{}) for a clear one; EVERY: both, true first.
+// HAS_TRUE = false: the axis has no `true` instances (a set flag then reaches nothing)
+template <bool HAS_TRUE = true, class F>
+void with_bool(int v, F&& f) {
+  if constexpr (HAS_TRUE) {
+    if (v != 0) f(std::true_type{});
+  }
+  if (v <= 0) f(std::false_type{});
+}
+
+// what a QP launch does (QpArgs::mode): prologue + PCG + epilogue, the Schur blocks only, the epilogue only
+enum { QP_MODE_PCG = 0, QP_MODE_SCHUR = 1, QP_MODE_DXU = 2 };
+
+// f(Int<MODE>{}) for the QP_MODE_* equal to mode (none for any other value); EVERY: all three, in order
+template <class F>
+void with_qp_mode(int mode, F&& f) {
+  if (mode == QP_MODE_PCG || mode == EVERY) f(Int<QP_MODE_PCG>{});
+  if (mode == QP_MODE_SCHUR || mode == EVERY) f(Int<QP_MODE_SCHUR>{});
+  if (mode == QP_MODE_DXU || mode == EVERY) f(Int<QP_MODE_DXU>{});
 }
 
 }  // namespace tmpc

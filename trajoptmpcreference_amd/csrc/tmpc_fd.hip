@@ -7,10 +7,6 @@
 
 namespace tmpc {
 
-__device__ __forceinline__ bool use_QF(const CostDev* C, int k, int N) {
-  return (k == N - 1) || (C->QF_start >= 0 && k >= C->QF_start);
-}
-
 // ======================================================================= per-knot forward dynamics
 // Solver mode: lane = (b, k), k < N-1.  Writes qdd (the point the gradient is
 // evaluated at, TrajoptPlant.py:313) and the dynamics defect

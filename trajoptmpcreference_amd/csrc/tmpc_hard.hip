@@ -44,10 +44,6 @@
 
 namespace tmpc {
 
-__device__ __forceinline__ bool h_use_QF(const CostDev* C, int k, int N) {
-  return (k == N - 1) || (C->QF_start >= 0 && k >= C->QF_start);
-}
-
 // the knot's rows in the reference order; returns the count (<= rmax).  slot (nullable) = t * 2 NJ + e,
 // the row's (limit kind, entry of [z - lb; ub - z]); *mask (nullable) = the active-set bitmask of the
 // knot, bit slot set for every violated entry (ACTIVE_SET's rows, FULL_SET's nonzero rows)
@@ -158,7 +154,7 @@ struct HGhat {
   const double* base;
   bool pk;
   __device__ __forceinline__ const double* x(const CostDev* C, int k, int N) const {
-    return pk ? base + (size_t)k * GS : base + (h_use_QF(C, k, N) ? NX * NX : 0);
+    return pk ? base + (size_t)k * GS : base + (use_QF(C, k, N) ? NX * NX : 0);
   }
   __device__ __forceinline__ const double* u(int k) const {
     return pk ? base + (size_t)k * GS + NX * NX : base + 2 * NX * NX;
@@ -176,7 +172,7 @@ __device__ __forceinline__ double hard_grad(const CostDev* __restrict__ C, const
   double g = 0.0;
   if (c < NX) {
     if (C->kind == COST_EE) return js ? js[k * (NX + NU) + c] : 0.0;
-    const double* Qk = h_use_QF(C, k, N) ? C->QF : C->Q;
+    const double* Qk = use_QF(C, k, N) ? C->QF : C->Q;
     for (int m = 0; m < NX; ++m) g += (xb[m * N + k] - xg[m]) * Qk[m * NX + c];
   } else if (k < K) {
     for (int m = 0; m < NU; ++m) g += ub[m * K + k] * C->R[m * NU + (c - NX)];
@@ -383,7 +379,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) k
   } else if (!per_knot) {   // the shared blocks' LDS copy
     lds_cdouble* gl = lds_ptr(s_gh);
     phase1([&](int kp, Cf cf, double* yo, const double* gk) {
-      return split_dot(gl + (h_use_QF(C, kp, N) ? NX * NX : 0), gl + 2 * NX * NX, kp, cf, yo, gk);
+      return split_dot(gl + (use_QF(C, kp, N) ? NX * NX : 0), gl + 2 * NX * NX, kp, cf, yo, gk);
     });
   } else {   // per-knot blocks (soft limits) in HBM
     phase1([&](int kp, Cf cf, double* yo, const double* gk) {

@@ -3,7 +3,7 @@
 // subclass on the host -- per knot the cost Hessian G_k (n x n with n = nx + nu, the x-u coupling
 // included; terminal nx x nx) and gradient g_k, the integrator's A_k, B_k and the defect c_k.  This is
 // the plugin-hook path of the drop-in (solver.py _sqp_hooks): the built-in plugins never take it
-// (their blocks are formed on the device, tmpc_kernels.hip k_qp), and the PCG is the same code
+// (their blocks are formed on the device, tmpc_qp.hip k_qp), and the PCG is the same code
 // (tmpc_pcg.h, restated by oracle/canon.c), so its counts are the fused kernel's.
 //
 //   k_ghat_full   (G_k + rho I)^-1 per (problem, knot): one wave per matrix, row r on lane r,
@@ -304,36 +304,32 @@ struct LaunchHooks {
     constexpr int n = 3 * NJ;
     hipLaunchKernelGGL((k_ghat_full<n>), dim3(B * N), dim3(64), 0, s, B, N, 2 * NJ, NJ, G, rho, Gh, err);
   }
+  // The k_qp_blocks instances of NJ joints, once: f(kernel) for those of `mode` and `rpl` rows per lane -- one for
+  // a launch's values, all of an axis for EVERY (set_lds)
+  template <class F>
+  static void for_qp_blocks(int mode, int rpl, F&& f) {
+    with_qp_mode(mode, [&](auto md) {
+      constexpr int MD = decltype(md)::value;
+      if (rpl == 1 || rpl == EVERY) f(k_qp_blocks<NJ, 1, 768, MD>);
+      if (rpl == 2 || rpl == EVERY) f(k_qp_blocks<NJ, 2, 512, MD>);
+    });
+  }
   static void qp(hipStream_t s, const QpArgs& a) {
     constexpr int NX = 2 * NJ;
     const int rows = a.N * NX;
     const int rpl = pcg_rpl(a.N, NX);
     const int threads = ((rows / rpl + 63) / 64) * 64;
     const size_t lds = qpb_lds_doubles(a.N, NX, NJ) * sizeof(double);
-    auto go = [&](auto* kernel) {
+    for_qp_blocks(a.mode, rpl, [&](auto* kernel) {
       hipLaunchKernelGGL(kernel, dim3(a.B), dim3(threads), lds, s, a.B, a.N, a.precond, a.G, a.g, a.A, a.Bm, a.cvec, a.err,
                          a.tol, a.max_iter, a.guess, a.iters, a.dx, a.du, a.lam, a.Sd, a.Sl, a.gam);
-    };
-#define TMPC_QPB_LAUNCH(MD)                     \
-    if (rpl == 1) go(k_qp_blocks<NJ, 1, 768, MD>); \
-    else go(k_qp_blocks<NJ, 2, 512, MD>);
-    if (a.mode == QP_MODE_PCG) {
-      TMPC_QPB_LAUNCH(QP_MODE_PCG)
-    } else if (a.mode == QP_MODE_SCHUR) {
-      TMPC_QPB_LAUNCH(QP_MODE_SCHUR)
-    } else {
-      TMPC_QPB_LAUNCH(QP_MODE_DXU)
-    }
-#undef TMPC_QPB_LAUNCH
+    });
   }
   static int set_lds(int bytes) {
     int e = 0;
-#define TMPC_QPB_ATTR(R, T, MD) \
-    e |= (int)hipFuncSetAttribute((const void*)k_qp_blocks<NJ, R, T, MD>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    TMPC_QPB_ATTR(1, 768, QP_MODE_PCG) TMPC_QPB_ATTR(2, 512, QP_MODE_PCG)
-    TMPC_QPB_ATTR(1, 768, QP_MODE_SCHUR) TMPC_QPB_ATTR(2, 512, QP_MODE_SCHUR)
-    TMPC_QPB_ATTR(1, 768, QP_MODE_DXU) TMPC_QPB_ATTR(2, 512, QP_MODE_DXU)
-#undef TMPC_QPB_ATTR
+    for_qp_blocks(EVERY, EVERY, [&](auto* kernel) {
+      e |= (int)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    });
     return e;
   }
 };

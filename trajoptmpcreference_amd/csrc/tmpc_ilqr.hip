@@ -21,10 +21,6 @@
 
 namespace tmpc {
 
-__device__ __forceinline__ bool use_QF(const CostDev* C, int k, int N) {
-  return (k == N - 1) || (C->QF_start >= 0 && k >= C->QF_start);
-}
-
 // ======================================================================= backward (Riccati) sweep
 template <int NJ, class R, bool TRK = false>
 struct IlqrLds {

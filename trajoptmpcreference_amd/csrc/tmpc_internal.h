@@ -1,4 +1,4 @@
-// Internal declarations shared by the kernels (the QP side in tmpc_kernels.hip, the solve loops' state
+// Internal declarations shared by the kernels (the QP side in tmpc_kernels.hip and tmpc_qp.hip, the solve loops' state
 // machine in tmpc_state.hip, ...) and the C-ABI / solver driver (tmpc_api.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -36,7 +36,7 @@ void launch_alive_list(hipStream_t s, int B, const int* alive, int* idx, int* cn
 // PRECOND_NONE: the identity preconditioner '0' (PCG.py:114-118)
 enum { PRECOND_J = 1, PRECOND_BJ = 2, PRECOND_SS = 3, PRECOND_NONE = 4 };
 enum { LS_MODE_INIT = 0, LS_MODE_STEP = 1 };
-enum { QP_MODE_PCG = 0, QP_MODE_SCHUR = 1, QP_MODE_DXU = 2 };
+// QP_MODE_*: tmpc_dispatch.h
 
 // per-problem solver state (device arrays, SoA)
 struct ProbState {
@@ -147,7 +147,7 @@ struct QpArgs : Batch {
   double *dx, *du;
   // launch_qp only
   const CostDev* C;
-  double dt;      // the Euler step of A_k / B_k (their structural rows are not read, tmpc_kernels.hip qp_schur_row)
+  double dt;      // the Euler step of A_k / B_k (their structural rows are not read, tmpc_qp.hip qp_schur_row)
   const double *x, *u;
   const int* active;       // launch_btsolve too
   const double* jsoft;     // soft limits: the knots' jacobian terms (else null)

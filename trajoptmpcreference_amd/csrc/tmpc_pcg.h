@@ -1,7 +1,7 @@
 // The block-tridiagonal PCG of the fused QP kernels (PCG.pcg / compute_preconditioner,
 // GBD-PCG-Python/PCG.py:66-212): lane geometry, register rows of S, LDS vectors, the
 // preconditioners, the products, the fixed-tree reductions and the CG iteration.  Shared by
-// tmpc_kernels.hip (k_qp, k_pcg) and tmpc_hooks.hip (k_qp_blocks, the plugin-hook QP): one
+// tmpc_qp.hip (k_qp, k_pcg) and tmpc_hooks.hip (k_qp_blocks, the plugin-hook QP): one
 // operation order, restated by oracle/canon.c.
 #pragma once
 #include "tmpc_internal.h"
