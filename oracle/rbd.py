@@ -6,8 +6,25 @@ checked against the reference's own parser output in
 tests/test_model.py (golden model_*.npz).
 
 Shapes: q, qd, qdd, u: (K, n); spatial vectors (K, 6); matrices (K, 6, 6).
+
+Precision.  Every routine works in the dtype of its state input (q or x) and returns that dtype; the model's
+coefficient arrays are cast to it first (cast_model).  float64 is the oracle the GPU's fp64 path is checked
+against, operation for operation what it always was; np.longdouble is the high-precision reference of the
+kernel-level dynamics tests (tests/test_oracle_dyn_hp.py, tests/test_gpu_dynamics_hp.py); float32 is the CPU
+candidate for the fp32 mode.  Scalars (gravity, dt) are Python floats: a NumPy float64 scalar would promote
+a float32 run.
 """
+import dataclasses
+
 import numpy as np
+
+
+def cast_model(model, dtype):
+    """The model with S, X0, Xa, Xb and I in `dtype` (itself when they already are)."""
+    dtype = np.dtype(dtype)
+    if all(getattr(model, k).dtype == dtype for k in ("S", "X0", "Xa", "Xb", "I")):
+        return model
+    return dataclasses.replace(model, **{k: getattr(model, k).astype(dtype) for k in ("S", "X0", "Xa", "Xb", "I")})
 
 
 def xmat(model, j, q):
@@ -29,7 +46,7 @@ def _mtv(M, v):
 def cross_operator(v):
     """crm(v)  (RBDReference.py:13-35)."""
     K = v.shape[0]
-    z = np.zeros(K)
+    z = np.zeros(K, dtype=v.dtype)
     return np.stack([
         np.stack([z, -v[:, 2], v[:, 1], z, z, z], 1),
         np.stack([v[:, 2], z, -v[:, 0], z, z, z], 1),
@@ -57,6 +74,13 @@ def fxv(f, t):
     return r
 
 
+def fxS(S, f):
+    """crf(S) f = fxv(S, f), the q_j derivative of X_j^T f_j before the transform.  The reference's fxS is
+    -mxS(S, f) = -crm(f) S (RBDReference.py:94-97), which equals crf(S) f for a revolute S = (w, 0) only: for
+    a prismatic S = (0, v), crf(S) f = [v x f_lin; 0] and -crm(f) S = [0; v x n]."""
+    return fxv(np.broadcast_to(S, f.shape), f)
+
+
 def vxIv(v, I):
     """v x* (I v)  (RBDReference.py:98-116)."""
     t = np.einsum("ij,kj->ki", I, v)
@@ -74,10 +98,12 @@ def rnea(model, q, qd, qdd=None, gravity=-9.81):
     """rnea_fpass + rnea_bpass (RBDReference.py:399-559).  Returns (c, v, a, f)
     with f *after* the backward accumulation, as the reference returns it."""
     K, n = q.shape
-    v = np.zeros((n, K, 6))
-    a = np.zeros((n, K, 6))
-    f = np.zeros((n, K, 6))
-    g = np.zeros((K, 6))
+    dt_ = q.dtype
+    model = cast_model(model, dt_)
+    v = np.zeros((n, K, 6), dtype=dt_)
+    a = np.zeros((n, K, 6), dtype=dt_)
+    f = np.zeros((n, K, 6), dtype=dt_)
+    g = np.zeros((K, 6), dtype=dt_)
     g[:, 5] = -gravity
     X = [xmat(model, j, q[:, j]) for j in range(n)]
     for j in range(n):
@@ -93,7 +119,7 @@ def rnea(model, q, qd, qdd=None, gravity=-9.81):
         if qdd is not None:
             a[j] = a[j] + S[None] * qdd[:, j:j + 1]
         f[j] = np.einsum("ij,kj->ki", model.I[j], a[j]) + vxIv(v[j], model.I[j])
-    c = np.zeros((K, n))
+    c = np.zeros((K, n), dtype=dt_)
     for j in range(n - 1, -1, -1):
         c[:, j] = f[j] @ model.S[j]
         p = model.parent[j]
@@ -105,15 +131,17 @@ def rnea(model, q, qd, qdd=None, gravity=-9.81):
 def rnea_grad(model, q, qd, qdd, gravity=-9.81):
     """rnea_grad (RBDReference.py:561-802) -> dc_du (K, n, 2n) = [dc/dq, dc/dqd]."""
     K, n = q.shape
+    dt_ = q.dtype
+    model = cast_model(model, dt_)
     c, v, a, f = rnea(model, q, qd, qdd, gravity)
     X = [xmat(model, j, q[:, j]) for j in range(n)]
     I = model.I
-    g = np.zeros((K, 6))
+    g = np.zeros((K, 6), dtype=dt_)
     g[:, 5] = -gravity
     # forward pass dq  (:561-633)
-    dv = np.zeros((n, n, K, 6))     # [ind][col]
-    da = np.zeros((n, n, K, 6))
-    df = np.zeros((n, n, K, 6))
+    dv = np.zeros((n, n, K, 6), dtype=dt_)     # [ind][col]
+    da = np.zeros((n, n, K, 6), dtype=dt_)
+    df = np.zeros((n, n, K, 6), dtype=dt_)
     for j in range(n):
         p = model.parent[j]
         S = model.S[j]
@@ -135,9 +163,9 @@ def rnea_grad(model, q, qd, qdd, gravity=-9.81):
             df[j, col] = df[j, col] + fxv(dv[j, col], Iv)
             df[j, col] = df[j, col] + fxv(v[j], np.einsum("ij,kj->ki", I[j], dv[j, col]))
     # forward pass dqd  (:635-690)
-    dvd = np.zeros((n, n, K, 6))
-    dad = np.zeros((n, n, K, 6))
-    dfd = np.zeros((n, n, K, 6))
+    dvd = np.zeros((n, n, K, 6), dtype=dt_)
+    dad = np.zeros((n, n, K, 6), dtype=dt_)
+    dfd = np.zeros((n, n, K, 6), dtype=dt_)
     for j in range(n):
         p = model.parent[j]
         S = model.S[j]
@@ -157,7 +185,7 @@ def rnea_grad(model, q, qd, qdd, gravity=-9.81):
             dfd[j, col] = dfd[j, col] + fxv(dvd[j, col], Iv)
             dfd[j, col] = dfd[j, col] + fxv(v[j], np.einsum("ij,kj->ki", I[j], dvd[j, col]))
     # backward pass dq  (:692-735)
-    dc_dq = np.zeros((K, n, n))
+    dc_dq = np.zeros((K, n, n), dtype=dt_)
     for j in range(n - 1, -1, -1):
         S = model.S[j]
         for col in range(n):
@@ -166,10 +194,10 @@ def rnea_grad(model, q, qd, qdd, gravity=-9.81):
         if p != -1:
             for col in range(n):
                 df[p, col] = df[p, col] + _mtv(X[j], df[j, col])
-            delta = _mtv(X[j], -mxS(S, f[j]))
+            delta = _mtv(X[j], fxS(S, f[j]))
             df[p, j] = df[p, j] + delta
     # backward pass dqd  (:737-771)
-    dc_dqd = np.zeros((K, n, n))
+    dc_dqd = np.zeros((K, n, n), dtype=dt_)
     for j in range(n - 1, -1, -1):
         S = model.S[j]
         for col in range(n):
@@ -184,11 +212,13 @@ def rnea_grad(model, q, qd, qdd, gravity=-9.81):
 def minv(model, q):
     """Analytic M^-1 (RBDReference.py:805-930), symmetrised from the upper triangle."""
     K, n = q.shape
+    dt_ = q.dtype
+    model = cast_model(model, dt_)
     X = [xmat(model, j, q[:, j]) for j in range(n)]
-    Minv = np.zeros((K, n, n))
-    F = np.zeros((n, K, 6, n))
-    U = np.zeros((n, K, 6))
-    Dinv = np.zeros((n, K))
+    Minv = np.zeros((K, n, n), dtype=dt_)
+    F = np.zeros((n, K, 6, n), dtype=dt_)
+    U = np.zeros((n, K, 6), dtype=dt_)
+    Dinv = np.zeros((n, K), dtype=dt_)
     IA = [np.broadcast_to(model.I[j], (K, 6, 6)).copy() for j in range(n)]
     for j in range(n - 1, -1, -1):
         S = model.S[j]
@@ -253,8 +283,9 @@ def euler_gradient(model, x, u, dt, gravity=-9.81):
     n = model.n
     K = x.shape[0]
     dqdd = forward_dynamics_gradient(model, x, u, gravity)
-    top = np.concatenate([np.zeros((n, n)), np.eye(n), np.zeros((n, n))], axis=1)
+    dt_ = x.dtype
+    top = np.concatenate([np.zeros((n, n), dtype=dt_), np.eye(n, dtype=dt_), np.zeros((n, n), dtype=dt_)], axis=1)
     dxdot = np.concatenate([np.broadcast_to(top, (K, n, 3 * n)), dqdd], axis=1)
-    A = np.eye(2 * n)[None] + dt * dxdot[:, :, :2 * n]
+    A = np.eye(2 * n, dtype=dt_)[None] + dt * dxdot[:, :, :2 * n]
     B = dt * dxdot[:, :, 2 * n:]
     return A, B

@@ -5,7 +5,8 @@ sensitive on the CPU by test_oracle_qp_hp.py): dense costs, non-zero goals, QF_s
 joints and the tree, soft limits at a non-trivial state, mixed rho inside a batch, batches of 65.
 
 Reference: oracle/qp_hp.py in long double on the GPU's OWN A, Bm, c (so the dynamics' rounding is not in S; A,
-Bm, c themselves are held to the oracle's at test_gpu_dynamics.py's 1e-12) and on the cost's G, g.  Errors are
+Bm, c themselves are held to the oracle's at test_gpu_dynamics.py's 1e-12, and to a long-double reference on
+general robots by test_gpu_dynamics_hp.py) and on the cost's G, g.  Errors are
 max|a - ref| / max|ref| (not floored at 1), the largest over the problems of a group that share a rho.  Bound,
 per quantity:  err_gpu <= 8 err_cpu64 + 4 * 2^-53,  err_cpu64 from the fp64 oracle (np.linalg.inv, schur_blocks,
 recover_dxu) on the same inputs; the floor covers a CPU result that is correctly rounded (a diagonal inverse)
@@ -32,8 +33,8 @@ gives the GPU's count and lambda bit for bit.
 Every figure is printed; each test raises its largest ratio as a warning (as test_gpu_ilqr_kernels.py).
 MEASURED on the MI355X, largest err_gpu / (err_cpu64 + floor / 8), every group within the margin 8:
                  Ghat   S     gamma  P     dxu   direct residual
-  one row        1.6    2.0   2.0    3.4   2.7   4.4      (1..7 joints and the tree, N = 2, 3, 8, no soft limits)
-  soft           1.9    1.6   1.8    2.5   2.0   4.2      (k_ginv_soft, both limit sets)
+  one row        1.6    2.0   1.7    3.4   3.3   4.4      (1..7 joints and the tree, N = 2, 3, 8, no soft limits)
+  soft           1.9    1.6   1.8    2.5   2.9   4.2      (k_ginv_soft, both limit sets)
   wide           1.3    1.3   2.4    3.6   1.7   3.4      (arm8, arm12: k_ginv at 32 lanes per matrix)
   two rows       1.5    1.1   1.2    1.3   1.8   -        (arm7 N = 55, arm12 N = 33)
   GM forced      0.83   0.81  1.2    0.64  1.6   -        (arm3 N = 8, arm1 N = 2)
@@ -41,6 +42,9 @@ MEASURED on the MI355X, largest err_gpu / (err_cpu64 + floor / 8), every group w
 A, Bm, c of the read-back are within 1e-12 of the oracle's on every group, arm12 included.  Hard limits: S_band
 within 1.8e-14 and gamma within 1.2e-14 of the oracle's (bound 1e-10); 4..18 hard rows per problem; arm3's PCG
 takes 43..100 iterations, arm6's runs to its cap of 100 on every problem (count and lambda still bit for bit).
+The one-row and soft rows were measured again after the RNEA gradient's prismatic term was corrected:
+tree4's A changed, and with it the tree's figures -- Ghat 1.2, S 1.2, gamma 1.7, P 2.2, dxu 3.3 (2.9 with soft
+limits), direct 1.9; it now holds the dxu maximum of both rows and no longer the one-row gamma maximum.
 No kernel was found wrong.
 """
 import warnings

@@ -854,11 +854,21 @@ __device__ __forceinline__ void rnea_grad_column(const MT& M, const R cq[NJ], co
     if (p >= 0) {
       add_mtvX<false>(M, j, cq[j], sq[j], df[j], df[p]);
       if (!colqd && j == col) {
-        // delta = X^T fxS(S, f) = -X^T (crm(f) S)
+        // delta = X^T crf(S) f, the q_j derivative of X_j^T f_j.  The reference's fxS(S, f) = -crm(f) S
+        // (RBDReference.py:94-97) equals crf(S) f for a revolute S = (w, 0) only; for a prismatic
+        // S = (0, v), crf(S) f = [v x f_lin; 0] while -crm(f) S = [0; v x n].  The
+        // revolute branch keeps the reference's form operation for operation.
         R cc[6];
-        crmS<false>(f[j], M, j, cc);
+        if (M->jtype[j] != 0) {
+          R Sj[6];
 #pragma unroll
-        for (int i = 0; i < 6; ++i) cc[i] = -cc[i];
+          for (int i = 0; i < 6; ++i) { Sj[i] = R(M->S[j][i]); cc[i] = 0.0; }
+          add_fxv<false>(Sj, f[j], cc);
+        } else {
+          crmS<false>(f[j], M, j, cc);
+#pragma unroll
+          for (int i = 0; i < 6; ++i) cc[i] = -cc[i];
+        }
         add_mtvX<false>(M, j, cq[j], sq[j], cc, df[p]);
       }
       add_mtvX<false>(M, j, cq[j], sq[j], f[j], f[p]);
