@@ -147,6 +147,7 @@ struct QpArgs : Batch {
   double *dx, *du;
   // launch_qp only
   const CostDev* C;
+  bool cost_diag;          // C is a QuadraticCost with CostDev.diag set (the host's copy; picks the PcgRowC instances)
   double dt;      // the Euler step of A_k / B_k (their structural rows are not read, tmpc_qp.hip qp_schur_row)
   const double *x, *u;
   const int* active;       // launch_btsolve too

@@ -142,6 +142,23 @@ struct PcgRow {
   double pr[NX];   // (S_kk)^-1 row  (J: pr[0] = 1 / S_ii)
 };
 
+// PcgRow without the structural zeros of its S_{k,k+1} row (k_qp's SUC instances: the Euler integrator with a
+// diagonal cost, tmpc_qp.hip qp_schur_row).  Row i of (A_k Ghat_x,k)^T has, among its first NX / 2 entries, one
+// non-zero, at j = i mod (NX / 2); the others are exact +0.  The products drop those terms: each is
+// fma(+0, v, acc) = acc for a finite v, and acc, which starts at +0, is never -0, so every chain keeps its
+// value bit for bit.  (A non-finite v would have made the dropped term NaN; the iteration's dot products
+// carry the same NaN to every row either way.)
+template <int NX>
+struct PcgRowC {
+  double sd[NX];
+  double sl[NX];
+  double su0;           // S_{k,k+1} row, entry i mod (NX / 2)
+  double suh[NX / 2];   // S_{k,k+1} row, entries NX / 2 .. NX - 1
+  double pr[NX];
+};
+template <class RT> struct RowSuPacked { static constexpr bool value = false; };
+template <int NX> struct RowSuPacked<PcgRowC<NX>> { static constexpr bool value = true; };
+
 // Past 1024 rows the four rows per lane no longer fit the register file (arm6
 // N = 128: 1536 rows x 48 doubles = 74k doubles > the CU's 64k-double VGPR
 // file), so the GM kernels keep S and P^-1 in HBM (L2 / MALL resident while a
@@ -226,8 +243,8 @@ __device__ __forceinline__ void pcg_lds_clear(double* lds, int N, int NX, int VR
 // In place, the row holds the not-yet-eliminated columns of [S_kk | I] and
 // the already-formed columns of the inverse; the arithmetic is operation for
 // operation that of the augmented [S_kk | I] elimination.
-template <int NX, int RPL>
-__device__ __forceinline__ void pcg_precondition(PcgRow<NX> (&R)[RPL], int precond, const PcgLane<NX, RPL>& ln,
+template <int NX, int RPL, class RT>
+__device__ __forceinline__ void pcg_precondition(RT (&R)[RPL], int precond, const PcgLane<NX, RPL>& ln,
                                                  int N, double* piv, double* Pd_block) {
   if (precond == PRECOND_NONE) {   // '0': P^-1 = I
     if (Pd_block && ln.valid) {
@@ -292,31 +309,70 @@ __device__ __forceinline__ void pcg_precondition(PcgRow<NX> (&R)[RPL], int preco
 // all RPL rows.  With one row per lane: three independent chains (latency);
 // with two: one chain per row (the rows interleave, and the VGPR budget of a
 // 2-waves-per-SIMD launch has no room for more accumulators).
+// PcgRowC: ku = the LDS index, relative to v, of the su0 term's operand v_{k+1}[i mod (NX / 2)] (pcg_run), read
+// once for all RPL rows (rows i and i + NX / 2 share it).  The term keeps its place in its chain: the first
+// of the su chain's own (one row per lane), after the sd term of j = i mod (NX / 2) in the single chain
+// (two rows per lane: lane-dependent, so under a branch).
 template <int NX, int RPL, class RT>
-__device__ __forceinline__ void pcg_spmv(const RT (&R)[RPL], const double* __restrict__ v, int kb,
+__device__ __forceinline__ void pcg_spmv(const RT (&R)[RPL], const double* __restrict__ v, int kb, int ku,
                                          double (&out)[RPL]) {
   const double* vm = v + kb - NX;
   constexpr int NC = RPL == 1 ? 3 : 1;
+  constexpr bool SUC = RowSuPacked<RT>::value;
   double a[NC][RPL];
 #pragma unroll
   for (int c = 0; c < NC; ++c)
 #pragma unroll
     for (int m = 0; m < RPL; ++m) a[c][m] = 0.0;
+  if constexpr (SUC) {
+    constexpr int NH = NX / 2;
+    const double pu = v[ku];
+    const int ju = ku - kb - NX;
+    if (NC == 3) {
 #pragma unroll
-  for (int j = 0; j < NX; ++j) {
-    const double p0 = vm[j], p1 = vm[NX + j], p2 = vm[2 * NX + j];
-#pragma unroll
-    for (int m = 0; m < RPL; ++m) {
-      a[0][m] += R[m].sl[j] * p0;
-      a[NC > 1 ? 1 : 0][m] += R[m].sd[j] * p1;
-      a[NC > 2 ? 2 : 0][m] += R[m].su[j] * p2;
+      for (int m = 0; m < RPL; ++m) a[NC - 1][m] += R[m].su0 * pu;
     }
-    // two rows per lane: bound the LDS loads in flight (each b128 holds 4
-    // VGPRs; all 18 hoisted would not fit next to the matrix rows): the
-    // accumulators are pinned here, and loads may not cross the fence
-    if (RPL > 1 && (j % 4) == 3) {
 #pragma unroll
-      for (int m = 0; m < RPL; ++m) asm volatile("" : "+v"(a[0][m])::"memory");
+    for (int j = 0; j < NX; ++j) {
+      const double p0 = vm[j], p1 = vm[NX + j];
+#pragma unroll
+      for (int m = 0; m < RPL; ++m) {
+        a[0][m] += R[m].sl[j] * p0;
+        a[NC > 1 ? 1 : 0][m] += R[m].sd[j] * p1;
+      }
+      if (j >= NH) {
+        const double p2 = vm[2 * NX + j];
+#pragma unroll
+        for (int m = 0; m < RPL; ++m) a[NC - 1][m] += R[m].suh[j - NH] * p2;
+      } else if (NC == 1 && j == ju) {
+#pragma unroll
+        for (int m = 0; m < RPL; ++m) a[0][m] += R[m].su0 * pu;
+      }
+      if (RPL > 1 && (j % 4) == 3) {   // two rows per lane: the dense form's bound on the loads in flight (below)
+#pragma unroll
+        for (int m = 0; m < RPL; ++m) asm volatile("" : "+v"(a[0][m])::"memory");
+      }
+      // one row per lane: without a bound the scheduler hoists all 31 operand doubles over the 43 of the row,
+      // and the allocator spills lane constants around the loop; the upper half's loads stay behind this fence
+      if (RPL == 1 && j == NH - 1) asm volatile("" : "+v"(a[0][0])::"memory");
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < NX; ++j) {
+      const double p0 = vm[j], p1 = vm[NX + j], p2 = vm[2 * NX + j];
+#pragma unroll
+      for (int m = 0; m < RPL; ++m) {
+        a[0][m] += R[m].sl[j] * p0;
+        a[NC > 1 ? 1 : 0][m] += R[m].sd[j] * p1;
+        a[NC > 2 ? 2 : 0][m] += R[m].su[j] * p2;
+      }
+      // two rows per lane: bound the LDS loads in flight (each b128 holds 4
+      // VGPRs; all 18 hoisted would not fit next to the matrix rows): the
+      // accumulators are pinned here, and loads may not cross the fence
+      if (RPL > 1 && (j % 4) == 3) {
+#pragma unroll
+        for (int m = 0; m < RPL; ++m) asm volatile("" : "+v"(a[0][m])::"memory");
+      }
     }
   }
 #pragma unroll
@@ -377,7 +433,7 @@ __device__ __forceinline__ double red_total(const double* red) {
 
 // t = r - (S_{k,k-1} w_{k-1} + S_{k,k+1} w_{k+1}) for this lane's rows
 template <int NX, int RPL, class RT>
-__device__ __forceinline__ void pcg_off(const RT (&R)[RPL], const double* __restrict__ w, int kb,
+__device__ __forceinline__ void pcg_off(const RT (&R)[RPL], const double* __restrict__ w, int kb, int ku,
                                         const double (&r)[RPL], double (&t)[RPL]) {
   const double* wm = w + kb - NX;
   constexpr int NC = RPL == 1 ? 2 : 1;
@@ -386,15 +442,39 @@ __device__ __forceinline__ void pcg_off(const RT (&R)[RPL], const double* __rest
   for (int c = 0; c < NC; ++c)
 #pragma unroll
     for (int m = 0; m < RPL; ++m) a[c][m] = 0.0;
+  if constexpr (RowSuPacked<RT>::value) {   // the su0 term in its place, as in pcg_spmv
+    constexpr int NH = NX / 2;
+    const double pu = w[ku];
+    const int ju = ku - kb - NX;
+    if (NC == 2) {
 #pragma unroll
-  for (int j = 0; j < NX; ++j) {
-    const double wl = wm[j], wu = wm[2 * NX + j];
-#pragma unroll
-    for (int m = 0; m < RPL; ++m) {
-      a[0][m] += R[m].sl[j] * wl;
-      a[NC - 1][m] += R[m].su[j] * wu;
+      for (int m = 0; m < RPL; ++m) a[NC - 1][m] += R[m].su0 * pu;
     }
-    PCG_LOAD_FENCE(RT, j, a[0])
+#pragma unroll
+    for (int j = 0; j < NX; ++j) {
+      const double wl = wm[j];
+#pragma unroll
+      for (int m = 0; m < RPL; ++m) a[0][m] += R[m].sl[j] * wl;
+      if (j >= NH) {
+        const double wu = wm[2 * NX + j];
+#pragma unroll
+        for (int m = 0; m < RPL; ++m) a[NC - 1][m] += R[m].suh[j - NH] * wu;
+      } else if (NC == 1 && j == ju) {
+#pragma unroll
+        for (int m = 0; m < RPL; ++m) a[0][m] += R[m].su0 * pu;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < NX; ++j) {
+      const double wl = wm[j], wu = wm[2 * NX + j];
+#pragma unroll
+      for (int m = 0; m < RPL; ++m) {
+        a[0][m] += R[m].sl[j] * wl;
+        a[NC - 1][m] += R[m].su[j] * wu;
+      }
+      PCG_LOAD_FENCE(RT, j, a[0])
+    }
   }
 #pragma unroll
   for (int m = 0; m < RPL; ++m) t[m] = r[m] - (NC == 2 ? a[0][m] + a[NC - 1][m] : a[0][m]);
@@ -422,6 +502,8 @@ __device__ __forceinline__ void pcg_run(const RT (&R)[RPL], const PcgLane<NX, RP
                                         const PcgLds& L, const double (&bv)[RPL], const double* guess_v, double tol,
                                         int max_iter, double* tn, double* tr, int* iters_out, double (&xv)[RPL]) {
   const int kb = ln.k * NX;
+  // PcgRowC: v_{k+1}[i mod (NX / 2)], the su0 terms' operand
+  const int ku = kb + NX + (ln.i < NX / 2 ? ln.i : ln.i - NX / 2);
   const int t = ln.t;
 #ifdef TMPC_PCG_STAMPS
   unsigned long long st_[16] = {}, st_prev_ = __builtin_amdgcn_s_memtime();
@@ -459,7 +541,7 @@ __device__ __forceinline__ void pcg_run(const RT (&R)[RPL], const PcgLane<NX, RP
   if (guess_v || IN_LDS) put(L.xbuf, xv);
   if (guess_v) {
     __syncthreads();
-    pcg_spmv<NX, RPL>(R, L.xbuf, kb, av);
+    pcg_spmv<NX, RPL>(R, L.xbuf, kb, ku, av);
 #pragma unroll
     for (int m = 0; m < RPL; ++m) rv[m] = bv[m] - av[m];
   }
@@ -468,7 +550,7 @@ __device__ __forceinline__ void pcg_run(const RT (&R)[RPL], const PcgLane<NX, RP
     if (!IN_LDS) put(L.xbuf, xv);
     __syncthreads();
     double e[RPL];
-    pcg_spmv<NX, RPL>(R, L.xbuf, kb, e);
+    pcg_spmv<NX, RPL>(R, L.xbuf, kb, ku, e);
 #pragma unroll
     for (int m = 0; m < RPL; ++m) e[m] = bv[m] - e[m];
     red_put(partial(e, e), redC);
@@ -493,7 +575,7 @@ __device__ __forceinline__ void pcg_run(const RT (&R)[RPL], const PcgLane<NX, RP
       put(L.wbuf, w);
       __syncthreads();
       double tv[RPL];
-      pcg_off<NX, RPL>(R, L.wbuf, kb, rv, tv);
+      pcg_off<NX, RPL>(R, L.wbuf, kb, ku, rv, tv);
       put(L.tbuf, tv);
       red_put(partial(w, tv), redC);
       __syncthreads();
@@ -521,7 +603,7 @@ __device__ __forceinline__ void pcg_run(const RT (&R)[RPL], const PcgLane<NX, RP
     PCG_STAMP(0);
     __syncthreads();                                   // B1: p
     PCG_STAMP(1);
-    pcg_spmv<NX, RPL>(R, L.pbuf, kb, av);
+    pcg_spmv<NX, RPL>(R, L.pbuf, kb, ku, av);
     double po[RPL];
 #pragma unroll
     for (int m = 0; m < RPL; ++m) po[m] = IN_LDS ? (ln.valid ? L.pbuf[ln.row(m)] : 0.0) : pv[m];
@@ -577,7 +659,7 @@ __device__ __forceinline__ void pcg_run(const RT (&R)[RPL], const PcgLane<NX, RP
       __syncthreads();                                 // B3: w
       PCG_STAMP(5);
       double tv[RPL];
-      pcg_off<NX, RPL>(R, L.wbuf, kb, rv, tv);
+      pcg_off<NX, RPL>(R, L.wbuf, kb, ku, rv, tv);
       put(L.tbuf, tv);
       red_put(partial(w, tv), redB);
       PCG_STAMP(6);

@@ -142,10 +142,13 @@ struct GhatSrc {
 // bottom NJ rows: a product's chain keeps its order term by term, a structural 1 or dt
 // is the same fma, a structural zero term is dropped (fma(0, g, acc) == acc for finite g, up to the
 // sign of a zero).  Half of A_k / B_k never leaves HBM for the QP, prologue and epilogue alike.
-template <int NJ, bool PK>
+// RT = PcgRowC (a diagonal cost: Ghat_x is diagonal, its off-diagonal entries +-0 from k_ginv): entry j < NJ
+// of the S_{k,k+1} row is fma(dt, +-0, +-0 + 0.0) = +0 but for j = i mod NJ, so only that entry (su0) and the
+// entries j >= NJ (suh) are formed, by the dense row's expressions.
+template <int NJ, bool PK, class RT>
 __device__ __forceinline__ double qp_schur_row(const CostDev* __restrict__ C, const QpStage& S,
                                                const GhatSrc<NJ, PK>& Gh, const double* __restrict__ g_lds,
-                                               double c_ki, int k, int i, int N, double dt, PcgRow<2 * NJ>& R) {
+                                               double c_ki, int k, int i, int N, double dt, RT& R) {
   constexpr int NX = 2 * NJ, NU = NJ;
   const int K = N - 1;
   const double* Gxk = Gh.x(C, k, N);
@@ -216,8 +219,12 @@ __device__ __forceinline__ double qp_schur_row(const CostDev* __restrict__ C, co
   }
   if (k < K) {
     const double* A = S.A + k * NX * NX;
+    if constexpr (RowSuPacked<RT>::value) {
+      const int j0 = i < NJ ? i : i - NJ;
+      R.su0 = fma(dt, Gxk[(j0 + NJ) * NX + i], Gxk[j0 * NX + i] + 0.0);
+    }
 #pragma unroll
-    for (int j = 0; j < NX; ++j) {
+    for (int j = RowSuPacked<RT>::value ? NJ : 0; j < NX; ++j) {
       double acc;
       if (j < NJ) {
         acc = fma(dt, Gxk[(j + NJ) * NX + i], Gxk[j * NX + i] + 0.0);
@@ -226,7 +233,8 @@ __device__ __forceinline__ double qp_schur_row(const CostDev* __restrict__ C, co
 #pragma unroll
         for (int m = 0; m < NX; ++m) acc += A[j * NX + m] * Gxk[m * NX + i];
       }
-      R.su[j] = acc;
+      if constexpr (RowSuPacked<RT>::value) R.suh[j - NJ] = acc;
+      else R.su[j] = acc;
     }
   }
   return gam;
@@ -240,7 +248,9 @@ __device__ __forceinline__ double qp_schur_row(const CostDev* __restrict__ C, co
 //           per lane, LDS vectors of QP_MAX_ROWS rows.
 //       TRK: the state goal of knot k from the goal window gw [B][N][NX] (tmpc_set_reference) in place of C->xg;
 //           the fixed-goal instances never touch gw.
-template <int NJ, int RPL, int MAXT, bool PK, int MODE, bool GM = false, bool TRK = false>
+//       SUC: the S_{k,k+1} rows without their structural zeros (PcgRowC, tmpc_pcg.h) -- a diagonal QuadraticCost
+//           without soft limits, register rows; bit for bit the dense instance's results.
+template <int NJ, int RPL, int MAXT, bool PK, int MODE, bool GM = false, bool TRK = false, bool SUC = false>
 __global__ void __launch_bounds__(MAXT) k_qp(const CostDev* __restrict__ C, PList P, int B, int N, double dt, int precond,
                                              const double* __restrict__ x, const double* __restrict__ u,
                                              const int* __restrict__ active, const double* __restrict__ Ginv,
@@ -254,6 +264,7 @@ __global__ void __launch_bounds__(MAXT) k_qp(const CostDev* __restrict__ C, PLis
                                              double* __restrict__ Sg, const double* __restrict__ gw) {
   constexpr int NX = 2 * NJ, NU = NJ;
   constexpr int VR = GM ? QP_MAX_ROWS : 1024;
+  static_assert(!SUC || (MODE == QP_MODE_PCG && !PK && !GM), "PcgRowC: the fused PCG on register rows, one Ghat per cost block");
   if (!P.has(blockIdx.x, B)) return;
   const int b = P.at(blockIdx.x);
   if (!active[b]) return;
@@ -296,7 +307,7 @@ __global__ void __launch_bounds__(MAXT) k_qp(const CostDev* __restrict__ C, PLis
     for (int m = 0; m < RPL; ++m) xv[m] = ln.valid ? lam_out[(size_t)b * rows + ln.row(m)] : 0.0;
     if (threadIdx.x == 0) iters[b] = 0;
   } else {
-  PcgRow<NX> R[RPL];
+  std::conditional_t<SUC, PcgRowC<NX>, PcgRow<NX>> R[RPL];
   double bv[RPL];
   // GM: this lane's rows of S / P^-1 in HBM (invalid lanes point at slot m N L and never use it)
   double* const Sgb = GM ? Sg + (size_t)b * 4 * NX * rows : nullptr;
@@ -308,8 +319,14 @@ __global__ void __launch_bounds__(MAXT) k_qp(const CostDev* __restrict__ C, PLis
   auto g_put = [&](int q, int m, int j, double v) { g_at(q, m)[(size_t)(j >> 1) * 2 * rows + (j & 1)] = v; };
 #pragma unroll
   for (int m = 0; m < RPL; ++m) {
+    if constexpr (SUC) {
+      R[m].su0 = 0.0;
 #pragma unroll
-    for (int j = 0; j < NX; ++j) R[m].sd[j] = R[m].sl[j] = R[m].su[j] = R[m].pr[j] = 0.0;
+      for (int j = 0; j < NX; ++j) R[m].sd[j] = R[m].sl[j] = R[m].suh[j >> 1] = R[m].pr[j] = 0.0;
+    } else {
+#pragma unroll
+      for (int j = 0; j < NX; ++j) R[m].sd[j] = R[m].sl[j] = R[m].su[j] = R[m].pr[j] = 0.0;
+    }
     bv[m] = 0.0;
     if (!ln.valid) continue;
     const int i = ln.r(m);
@@ -555,19 +572,23 @@ static QpGeom qp_geom(int nj, int N, int mode) {
 // The k_qp instances of NJ joints, once.  f(kernel) for those of the QP mode, the flags pk (per-knot Ghat: soft
 // limits) and trk (a goal window: the tracking instances) and the geometry g: a launch's values reach one
 // instance, EVERY in place of a value all of that axis (pcg_set_max_lds; rpl EVERY: every geometry).
-// A wide model has no soft-limit and no HBM-row instances.
+// A wide model has no soft-limit and no HBM-row instances.  suc: the compressed S_{k,k+1} rows (launch_qp_nj) --
+// instances for the fused PCG on register rows without soft limits only; never with gm.
 template <int NJ, class F>
-void for_qp(int mode, int pk, int trk, int rpl, bool gm, F&& f) {
+void for_qp(int mode, int pk, int trk, int suc, int rpl, bool gm, F&& f) {
   with_qp_mode(mode, [&](auto md) {
     with_bool<!kWide<NJ>>(pk, [&](auto p) {
       with_bool(trk, [&](auto t) {
         constexpr int MD = decltype(md)::value;
         constexpr bool PK = decltype(p)::value, TRK = decltype(t)::value;
-        if constexpr (!kWide<NJ>) {
-          if (rpl == EVERY || gm) f(k_qp<NJ, 2, QP_MAX_ROWS / 2, PK, MD, true, TRK>);
-        }
-        if (rpl == EVERY || (!gm && rpl == 1)) f(k_qp<NJ, 1, 768, PK, MD, false, TRK>);
-        if (rpl == EVERY || (!gm && rpl == 2)) f(k_qp<NJ, 2, 512, PK, MD, false, TRK>);
+        with_bool<MD == QP_MODE_PCG && !PK && !kWide<NJ>>(suc, [&](auto c) {
+          constexpr bool SUC = decltype(c)::value;
+          if constexpr (!kWide<NJ> && !SUC) {
+            if (rpl == EVERY || gm) f(k_qp<NJ, 2, QP_MAX_ROWS / 2, PK, MD, true, TRK>);
+          }
+          if (rpl == EVERY || (!gm && rpl == 1)) f(k_qp<NJ, 1, 768, PK, MD, false, TRK, SUC>);
+          if (rpl == EVERY || (!gm && rpl == 2)) f(k_qp<NJ, 2, 512, PK, MD, false, TRK, SUC>);
+        });
       });
     });
   });
@@ -578,7 +599,10 @@ static void launch_qp_nj(hipStream_t s, const QpArgs& a, const QpGeom& g) {
   constexpr int NX = 2 * NJ;
   const int threads = ((a.N * NX / g.rpl + 63) / 64) * 64;
   const size_t lds = qp_lds_doubles(a.N, NX, NJ, g.gm ? QP_MAX_ROWS : 1024) * sizeof(double);
-  for_qp<NJ>(a.mode, a.jsoft != nullptr, a.gw != nullptr, g.rpl, g.gm, [&](auto* kernel) {
+  // a diagonal QuadraticCost (CostDev.diag) makes Ghat_x diagonal: the fused PCG on register rows runs on the
+  // S_{k,k+1} rows without their structural zeros (TMPC_GENERIC_COST=1 clears diag: the dense instance)
+  const bool suc = a.cost_diag && !a.jsoft && !g.gm && a.mode == QP_MODE_PCG && !kWide<NJ>;
+  for_qp<NJ>(a.mode, a.jsoft != nullptr, a.gw != nullptr, suc, g.rpl, g.gm, [&](auto* kernel) {
     hipLaunchKernelGGL(kernel, dim3(a.B), dim3(threads), lds, s, a.C, a.P, a.B, a.N, a.dt, a.precond, a.x, a.u, a.active,
                        a.G, a.A, a.Bm, a.cvec, a.tol, a.max_iter, a.iters, a.dx, a.du, a.lam, a.Sd, a.Sl, a.gam, a.Pd,
                        a.jsoft, a.guess, a.Sg, a.gw);
@@ -597,7 +621,7 @@ int pcg_set_max_lds() {
     set(k_pcg<decltype(nx)::value, 1, 768>);
     set(k_pcg<decltype(nx)::value, 2, 512>);
   });
-  for_each_nj<1, NJMAX>([&](auto nj) { for_qp<decltype(nj)::value>(EVERY, EVERY, EVERY, EVERY, false, set); });
+  for_each_nj<1, NJMAX>([&](auto nj) { for_qp<decltype(nj)::value>(EVERY, EVERY, EVERY, EVERY, EVERY, false, set); });
   return err;
 }
 

@@ -47,6 +47,7 @@ void bind_work(const tmpc_ctx* ctx, int N, double dt, const double* d_x, const d
   w.dyn.N = w.qp.N = w.gs.N = N; w.dyn.dt = w.qp.dt = dt; w.dyn.x = w.qp.x = w.gs.x = d_x;
   w.dyn.u = w.qp.u = w.gs.u = d_u; w.dyn.need = st.need_grad; w.qp.active = w.gs.active = st.active; w.gs.rho = st.rho;
   w.qp.C = w.gs.C = ctx->dcost; w.gs.Cs = ctx->dlim;
+  w.qp.cost_diag = ctx->hcost.kind == COST_QUADRATIC && ctx->hcost.diag != 0;
 }
 
 // the banded QP: rows + layout + Schur band, the solve, dxu
