@@ -688,6 +688,56 @@ __device__ __forceinline__ void fd_aba(const MT& M, const R cq[NJ], const R sq[N
   }
 }
 
+// ----------------------------------------------------------------- integrator
+// The plant step x+ = x + dt [qd; qdd(x, u)] (TrajoptPlant.py:92-99, explicit Euler) and its Jacobians.
+// Everything that knows which integrator the solvers use is in this section; its users are k_qp_fd,
+// k_ls_terms, k_unit_fd, k_rollout, k_mpc_advance (tmpc_fd.hip), k_ilqr_forward (tmpc_ilqr.hip) and
+// grad_lane_store (tmpc_kernels.hip).  The MPC step's x_pred against the rollout, the line search's defect
+// against the QP's c and the stream against the batch agree bit for bit because they all run this text.
+
+// qdd(x, u) in the instance's scalar type R, fp64 in and out (R = double: no conversion is left).
+// The six kernels hold these lines as text, each fused with its own loads, and name this function in a
+// comment: called through it, in either form of its arguments, about half of their instances change
+// registers, scratch or occupancy (profiles/euler_step/README.md), and the rule of that change was that no
+// instance may.  An integrator whose qdd is evaluated differently changes this function and those six loops.
+template <int NJ, bool CHAIN, class R, class MT>
+__device__ __forceinline__ void state_qdd(const MT& M, const double* q, const double* qd, const double* u,
+                                          double* qdd) {
+  R cq[NJ], sq[NJ], qdr[NJ], ur[NJ], qddr[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    qdr[j] = R(qd[j]);
+    ur[j] = R(u[j]);
+    joint_cs(M, j, R(q[j]), cq[j], sq[j]);
+  }
+  fd_aba<NJ, CHAIN>(M, cq, sq, qdr, ur, qddr);
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) qdd[j] = double(qddr[j]);
+}
+
+// one entry of x + dt xdot: the product and the sum each rounded once, as NumPy does (no contraction into an
+// FMA, so the step is the same bits wherever it runs)
+__device__ __forceinline__ double euler_next(double x, double dt, double xdot) {
+  return __dadd_rn(x, __dmul_rn(dt, xdot));
+}
+
+// Column col of the step's Jacobians, joint r's two rows: A = I + dt [[0, I], [dqdd_q, dqdd_qd]],
+// B = dt [[0], [Minv]] (TrajoptPlant.py:100-108), with acc = dqdd[r][col] and Mi = Minv.  The first NJ rows of
+// A hold exactly 1, dt and 0 and those of B +0: k_qp (tmpc_qp.hip) builds its rows on that structure.
+template <int NJ>
+__device__ __forceinline__ void euler_jac_store(double dt, int r, int col, double acc, const double* __restrict__ Mi,
+                                                double* __restrict__ A, double* __restrict__ Bm) {
+  constexpr int NX = 2 * NJ;
+  if (A) {
+    A[r * NX + col] = (r == col ? 1.0 : 0.0) + dt * (col == NJ + r ? 1.0 : 0.0);
+    A[(NJ + r) * NX + col] = (NJ + r == col ? 1.0 : 0.0) + dt * acc;
+  }
+  if (Bm && col < NJ) {
+    Bm[r * NJ + col] = 0.0;
+    Bm[(NJ + r) * NJ + col] = dt * Mi[r * NJ + col];
+  }
+}
+
 // ----------------------------------------------------------------- analytic M^-1, one column
 // Computes Minv[r][col] for r <= col (the upper triangle the reference fills
 // before symmetrising, :908-930) following minv_bpass / minv_fpass

@@ -27,6 +27,7 @@ __global__ void __launch_bounds__(256) k_qp_fd(MT M, PList P, int B, int N, doub
   if (!need[b]) return;
   const double* xb = x + (size_t)b * NX * N;
   const double* ub = u + (size_t)b * NJ * K;
+  // (state_qdd of tmpc_device.h's integrator section, as text: see profiles/euler_step/README.md)
   double q[NJ], qd[NJ], qdd[NJ];
   R qdr[NJ], ur[NJ], qddr[NJ], cq[NJ], sq[NJ];
 #pragma unroll
@@ -46,9 +47,8 @@ __global__ void __launch_bounds__(256) k_qp_fd(MT M, PList P, int B, int N, doub
   double* cb = cvec + (size_t)b * N * NX;
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
-    // x_{k+1} = x_k + dt * [qd; qdd]  (TrajoptPlant.py:95-97), rounded as NumPy does
-    const double xq = __dadd_rn(q[j], __dmul_rn(dt, qd[j]));
-    const double xv = __dadd_rn(qd[j], __dmul_rn(dt, qdd[j]));
+    const double xq = euler_next(q[j], dt, qd[j]);
+    const double xv = euler_next(qd[j], dt, qdd[j]);
     cb[(k + 1) * NX + j] = xb[j * N + k + 1] - xq;
     cb[(k + 1) * NX + NJ + j] = xb[(NJ + j) * N + k + 1] - xv;
   }
@@ -178,6 +178,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
     }
     cost += 0.5 * vr;
     // dynamics defect at the trial point
+    // (state_qdd of tmpc_device.h's integrator section, as text: see profiles/euler_step/README.md)
     double qd[NJ], qdd[NJ];
     R cq[NJ], sq[NJ], qdr[NJ], ur[NJ], qddr[NJ];
 #pragma unroll
@@ -195,7 +196,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
       const double dxn = dxb ? dxb[(k + 1) * NX + m] : 0.0;
       const double xn = dxb ? xb[m * N + k + 1] - al * dxn : xb[m * N + k + 1];
       const double xdot = m < NJ ? qd[m] : qdd[m - NJ];
-      const double f = __dadd_rn(xk[m], __dmul_rn(dt, xdot));
+      const double f = euler_next(xk[m], dt, xdot);
       viol += fabs(xn - f);
     }
   } else {
@@ -236,6 +237,7 @@ __global__ void __launch_bounds__(256) k_unit_fd(MT M, int K, double dt,
   constexpr int NX = 2 * NJ;
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= K) return;
+  // (state_qdd of tmpc_device.h's integrator section, as text: see profiles/euler_step/README.md)
   double q[NJ], qd[NJ], qdd[NJ];
   R qdr[NJ], ur[NJ], qddr[NJ], cq[NJ], sq[NJ];
 #pragma unroll
@@ -253,8 +255,8 @@ __global__ void __launch_bounds__(256) k_unit_fd(MT M, int K, double dt,
   for (int j = 0; j < NJ; ++j) {
     qdd_out[(size_t)k * NJ + j] = qdd[j];
     if (xnext) {
-      xnext[(size_t)k * NX + j] = __dadd_rn(q[j], __dmul_rn(dt, qd[j]));
-      xnext[(size_t)k * NX + NJ + j] = __dadd_rn(qd[j], __dmul_rn(dt, qdd[j]));
+      xnext[(size_t)k * NX + j] = euler_next(q[j], dt, qd[j]);
+      xnext[(size_t)k * NX + NJ + j] = euler_next(qd[j], dt, qdd[j]);
     }
   }
 }
@@ -276,6 +278,7 @@ __global__ void __launch_bounds__(64) k_rollout(MT M, PList P, int B, int N, dou
 #pragma unroll
   for (int j = 0; j < NJ; ++j) { q[j] = xb[j * N]; qd[j] = xb[(NJ + j) * N]; }
   for (int k = 0; k < K; ++k) {
+    // (state_qdd of tmpc_device.h's integrator section, as text: see profiles/euler_step/README.md)
     double qdd[NJ];
     R ur[NJ], qdr[NJ], qddr[NJ], cq[NJ], sq[NJ];
 #pragma unroll
@@ -289,8 +292,8 @@ __global__ void __launch_bounds__(64) k_rollout(MT M, PList P, int B, int N, dou
     for (int j = 0; j < NJ; ++j) qdd[j] = double(qddr[j]);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      const double nq = __dadd_rn(q[j], __dmul_rn(dt, qd[j]));
-      const double nv = __dadd_rn(qd[j], __dmul_rn(dt, qdd[j]));
+      const double nq = euler_next(q[j], dt, qd[j]);
+      const double nv = euler_next(qd[j], dt, qdd[j]);
       q[j] = nq;
       qd[j] = nv;
       xb[j * N + k + 1] = nq;
@@ -301,9 +304,8 @@ __global__ void __launch_bounds__(64) k_rollout(MT M, PList P, int B, int N, dou
 
 // ======================================================================= MPC advance (oracle/mpc.py, AdvanceArgs)
 // Everything the MPC loop does between two horizon solves, one 64-lane workgroup per problem.  Lane 0 applies the
-// first control to the plant, x_next = integrator(x_0, u_0) (TrajoptPlant.py:92-99): joint_cs and fd_aba in fp64,
-// then q + dt qd and qd + dt qdd as one __dmul_rn and one __dadd_rn each (no contraction: the executed states
-// are the same bits wherever the step runs), while lane 1 copies the solve's status; then the lanes spread along
+// first control to the plant, x_next = integrator(x_0, u_0): the integrator section of tmpc_device.h in fp64
+// (state_qdd<double>'s lines, euler_next), while lane 1 copies the solve's status; then the lanes spread along
 // the knots, 64 per chunk, for the warm start's shift (x_k <- x_{k+1}, u_k <- u_{k+1}, last knot kept,
 // x_0 <- x_next).  A row shifts in place, so a chunk's last lane reads the element the next chunk's first lane
 // writes (64 c + 64): every lane loads its knot k + 1 of all rows -- x, u and the warm lambda's block, which
@@ -326,6 +328,7 @@ __global__ void __launch_bounds__(64) k_mpc_advance(MT M, AdvanceArgs a) {
   __shared__ double xn[NX];
   if (t == 0) {
     // the simulated plant is fp64 in every precision mode
+    // (state_qdd<double> of tmpc_device.h's integrator section, as text: see profiles/euler_step/README.md)
     double q[NJ], qd[NJ], uu[NJ], qdd[NJ], cq[NJ], sq[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -337,8 +340,8 @@ __global__ void __launch_bounds__(64) k_mpc_advance(MT M, AdvanceArgs a) {
     fd_aba<NJ, CHAIN>(M, cq, sq, qd, uu, qdd);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      xn[j] = __dadd_rn(q[j], __dmul_rn(a.dt, qd[j]));
-      xn[NJ + j] = __dadd_rn(qd[j], __dmul_rn(a.dt, qdd[j]));
+      xn[j] = euler_next(q[j], a.dt, qd[j]);
+      xn[NJ + j] = euler_next(qd[j], a.dt, qdd[j]);
     }
     if (a.x_out) {
 #pragma unroll

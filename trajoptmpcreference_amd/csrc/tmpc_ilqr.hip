@@ -889,6 +889,7 @@ __global__ void __launch_bounds__(64) k_ilqr_forward(MT Mg, const CostDev* __res
     J = J + knot_quad_cost<NJ, TRK>(C, TRK ? gh : nullptr, k, N, xh, uh, term);
     IL_STAMP(1);
     if (!term && !init) {
+      // (state_qdd of tmpc_device.h's integrator section, as text: see profiles/euler_step/README.md)
       double qd[NJ], qdd[NJ];
       R cq[NJ], sq[NJ], qdr[NJ], ur[NJ], qddr[NJ];
 #pragma unroll
@@ -904,8 +905,8 @@ __global__ void __launch_bounds__(64) k_ilqr_forward(MT Mg, const CostDev* __res
       for (int j = 0; j < NJ; ++j) qdd[j] = double(qddr[j]);
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
-        const double nq = __dadd_rn(xh[j], __dmul_rn(dt, qd[j]));
-        const double nv = __dadd_rn(xh[NJ + j], __dmul_rn(dt, qdd[j]));
+        const double nq = euler_next(xh[j], dt, qd[j]);
+        const double nv = euler_next(xh[NJ + j], dt, qdd[j]);
         xh[j] = nq;
         xh[NJ + j] = nv;
       }

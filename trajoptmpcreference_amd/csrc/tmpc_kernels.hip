@@ -67,8 +67,8 @@ __global__ void __launch_bounds__(256) k_qp_minv(MT M, PList P, int B, int N,
 
 // ======================================================================= gradient columns -> A, B
 // lane = (b, k, col), col < 2 NJ.  dqdd[:, col] = -Minv dc[:, col]
-// (TrajoptPlant.py:313-316); A = I + dt [[0, I], [dqdd_q, dqdd_qd]],
-// B = dt [[0], [Minv]] (TrajoptPlant.py:100-108).
+// (TrajoptPlant.py:313-316); A and B from it by the integrator section of
+// tmpc_device.h (euler_jac_store).
 template <int NJ, bool CHAIN, class R, class MT>
 __device__ __forceinline__ void grad_lane_store(const MT& M, double dt, const double q[NJ],
                                                 const double qd[NJ], const double qdd[NJ],
@@ -94,14 +94,7 @@ __device__ __forceinline__ void grad_lane_store(const MT& M, double dt, const do
       dqdd[r * 3 * NJ + col] = acc;
       if (col < NJ) dqdd[r * 3 * NJ + NX + col] = Mi[r * NJ + col];
     }
-    if (A) {
-      A[r * NX + col] = (r == col ? 1.0 : 0.0) + dt * (col == NJ + r ? 1.0 : 0.0);
-      A[(NJ + r) * NX + col] = (NJ + r == col ? 1.0 : 0.0) + dt * acc;
-    }
-    if (Bm && col < NJ) {
-      Bm[r * NJ + col] = 0.0;
-      Bm[(NJ + r) * NJ + col] = dt * Mi[r * NJ + col];
-    }
+    euler_jac_store<NJ>(dt, r, col, acc, Mi, A, Bm);
   }
 }
 

@@ -136,9 +136,8 @@ struct GhatSrc {
   }
 };
 
-// A_k, B_k of the Euler integrator (TrajoptPlant.py:92-108) as k_qp_grad writes them:
-//   A_k = [[I, dt I], [dt dqdd_q, I + dt dqdd_qd]],   B_k = [[0], [dt M^-1]].
-// Their first NJ rows are structural -- exactly 1, dt and 0 -- so the fused QP kernel reads only the
+// A_k, B_k of the integrator as k_qp_grad writes them: euler_jac_store in the integrator section of
+// tmpc_device.h.  Their first NJ rows are structural -- exactly 1, dt and 0 -- so the fused QP kernel reads only the
 // bottom NJ rows: a product's chain keeps its order term by term, a structural 1 or dt
 // is the same fma, a structural zero term is dropped (fma(0, g, acc) == acc for finite g, up to the
 // sign of a zero).  Half of A_k / B_k never leaves HBM for the QP, prologue and epilogue alike.
